@@ -2,7 +2,7 @@
 """bench.py -- windows/s of the MI355X spectrum hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config north_star]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One step = one launch of the hot path over the configuration's whole window
 batch, input already resident in HBM (series generated on device).  One
@@ -26,9 +26,15 @@ phase is untimed and reported in the line ("settle").  The timed region is
 exactly K full steps; `roofline.kernel_ms` comes from HIP events recorded on
 the launch stream around those same K steps.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-`roofline` and `cpu_baseline` (the oracle -- CPU restatement of the reference
-path -- timed on a bounded sample on this host).
+A plain run sets up, settles, warms up, times the K steps and prints ONE JSON
+line (rank 0) with the driver's contract fields plus `roofline` (HIP events
+around the same K steps; traffic from the committed profiles/traffic.json).
+--dump-outputs DIR also writes what the last timed step computed, as
+DIR/<name>.npy (`dump_outputs`).  --full adds what takes runs of its own, after
+the timed region: `cpu_baseline` / `cpu_baseline_all_cores` (the oracle -- CPU
+restatement of the reference path -- timed on a bounded sample on this host)
+and, with --pmc auto, this run's HBM traffic from rocprofv3 passes over child
+runs of the same command.
 """
 from __future__ import annotations
 
@@ -60,7 +66,15 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="north_star", choices=CONFIGS)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the 1-core CPU baseline sample")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64; "
+                         "a fixed, seeded sample of rows when the outputs exceed DUMP_BUDGET_BYTES)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also time the CPU baselines (--cpu-seconds, --no-cpu-baseline) and, with "
+                         "--pmc auto, measure this run's HBM traffic (rocprofv3 passes over child runs); off: the line "
+                         "carries cpu_baseline null and the committed profiles/traffic.json")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="--full: budget of the 1-core CPU baseline sample")
     ap.add_argument("--algo", default="auto", choices=["auto", "fft", "slide"],
                     help="hop = 1 power batches: seeded sliding DFT or FFT per window (wsp_plan_set_algorithm)")
     ap.add_argument("--slide-seg", type=int, default=0, help="windows per sliding-DFT workgroup (0 = library policy)")
@@ -93,8 +107,8 @@ def parse(argv=None):
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
                     help="roofline.traffic from this run: rocprofv3 FETCH_SIZE / WRITE_SIZE passes over a 3-step run "
                          "of the same command, as child processes after the timed region (scripts/pmc_traffic.py); "
-                         "auto = on for a one-GPU line with its CPU baseline (the driver's default line and the "
-                         "closing check), off for A/B and shard runs, which keep the committed profiles/traffic.json")
+                         "auto = on for a one-GPU --full line with its CPU baseline (the closing check), off for plain, "
+                         "A/B and shard runs, which keep the committed profiles/traffic.json")
     ap.add_argument("--plan-only", action="store_true",
                     help="print every rank's shard of the batch and exit, without touching a GPU (CPU tests)")
     return ap.parse_args(argv)
@@ -315,6 +329,10 @@ class Workload:
     def step(self):
         raise NotImplementedError
 
+    def outputs(self):
+        """[(name, 2-D tensor: one row per window)]: the device arrays a caller of step() receives."""
+        raise NotImplementedError
+
     def close(self):
         pass
 
@@ -438,6 +456,9 @@ class SingleBatch(Workload):
     def step(self):
         self.plan.execute(*self._args)
 
+    def outputs(self):
+        return [("out", self.out.view(self.windows, -1))]
+
     def close(self):
         self.plan.close()
 
@@ -489,6 +510,7 @@ class C5Batch(Workload):
             if slide_seg:
                 self.group.set_segment(slide_seg)
             self._ptrs = ([x.data_ptr() for x in self.series], [o.data_ptr() for o in self.outs])
+            self._nws = [p[2] for p in pieces]
             self.algorithm = "slide-group" + {"group-per-length": "-per-length", "group-mixed-b4": "-mixed-b4", "group-mixed-tail-half": "-mixed-tail-half", "group-mixed-uniform": "-mixed-uniform", "group-mixed-lds-seeds": "-mixed-lds-seeds", "group-mixed-plain-stores": "-mixed-plain-stores"}.get(c5_mode, "")
             self.layout = {"mode": "group", "launches": self.group.launches, "streams": c5_streams or "library default",
                            "segment": slide_seg or "auto", "pieces": len(pieces)}
@@ -558,6 +580,11 @@ class C5Batch(Workload):
         for st in self.streams:
             self.stream.wait_stream(st)
 
+    def outputs(self):
+        outs = self.outs if self.group is not None else [j[2] for j in self.jobs]
+        nws = self._nws if self.group is not None else [j[0].n_windows for j in self.jobs]
+        return [(f"piece{i:02d}", o.view(nw, -1)) for i, (o, nw) in enumerate(zip(outs, nws))]
+
     def close(self):
         if self.group is not None:
             self.group.close()
@@ -566,12 +593,35 @@ class C5Batch(Workload):
             j[0].close()
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files of one run together (the cap is 64 MB)
+
+
+def dump_outputs(wl: Workload, directory: str, rank: int, world: int) -> None:
+    """--dump-outputs: the arrays the last timed step left in the workload's output buffers, as
+    <directory>/<name>.npy in the run's own precision (rank<r>_<name>.npy with more than one rank).  Outputs
+    beyond DUMP_BUDGET_BYTES are cut to a sample of whole rows (one row = one window's record), each array
+    its share of the budget by size, the rows drawn by a generator seeded with the array's position, so the
+    same arguments always keep the same rows."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    arrays = wl.outputs()
+    total = sum(t.numel() * t.element_size() for _, t in arrays)
+    for i, (name, t) in enumerate(arrays):
+        rows, row_bytes = t.shape[0], t.shape[1] * t.element_size()
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, min(rows, int(DUMP_BUDGET_BYTES * (rows * row_bytes / total)) // row_bytes))
+            if keep < rows:
+                idx = np.sort(np.random.default_rng(i).choice(rows, size=keep, replace=False))
+                t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(directory, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), t.cpu().numpy())
+
+
 def want_pmc(args) -> bool:
-    """--pmc auto: this run's traffic for a one-GPU line that carries its CPU baseline (the driver's default line,
-    the closing check's lines), never inside a PMC child or for an emulated shard."""
+    """--pmc auto: this run's traffic for a one-GPU --full line that carries its CPU baseline (the closing check's
+    lines), never for a plain run, inside a PMC child or for an emulated shard."""
     if os.environ.get("WSP_BENCH_PMC_CHILD") or args.emulate_shard:
         return False
-    return args.pmc == "on" or (args.pmc == "auto" and not args.no_cpu_baseline)
+    return args.pmc == "on" or (args.pmc == "auto" and args.full and not args.no_cpu_baseline)
 
 
 def run_pmc(args, argv):
@@ -579,7 +629,8 @@ def run_pmc(args, argv):
     this same command; the per-step bytes, or None (no rocprofv3, a failed or timed-out pass)."""
     sys.path.insert(0, str(ROOT / "scripts"))
     import pmc_traffic
-    drop = {"--steps": 1, "--warmup": 1, "--pmc": 1, "--cpu-seconds": 1, "--no-cpu-baseline": 0, "--no-settle": 0}
+    drop = {"--steps": 1, "--warmup": 1, "--pmc": 1, "--cpu-seconds": 1, "--no-cpu-baseline": 0, "--no-settle": 0,
+            "--full": 0, "--dump-outputs": 1}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
@@ -647,10 +698,12 @@ def main(argv=None):
     total_windows = ctl.sum(float(wl.windows * args.steps))
     value = total_windows / secs
     baseline = baseline_all = None
-    # The CPU baseline beside every line (north star: "next to the reference CPU path timed on the GPU
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank, world)
+    # --full: the CPU baseline beside the line (north star: "next to the reference CPU path timed on the GPU
     # box's own host cores in the same run"), on rank 0 after the timed region, so it never overlaps the
-    # GPU timing; with N > 1 ranks the sample is halved to keep the driver's 1/2/4/8 sweep short.
-    if rank == 0 and not args.no_cpu_baseline and wl.cpu_cfg is not None:
+    # GPU timing; with N > 1 ranks the sample is halved to keep a 1/2/4/8 sweep short.
+    if rank == 0 and args.full and not args.no_cpu_baseline and wl.cpu_cfg is not None:
         budget = args.cpu_seconds if world == 1 else args.cpu_seconds / 2
         baseline = cpu_baseline(wl.cpu_cfg[0], wl.cpu_cfg[1], budget)
         baseline_all = cpu_baseline(wl.cpu_cfg[0], wl.cpu_cfg[1], budget / 2, cpu_threads())

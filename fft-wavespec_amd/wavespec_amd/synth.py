@@ -23,15 +23,33 @@ def random_walk(length: int, seed: int, step: float = 1e-4) -> np.ndarray:
     return 1.1 + np.cumsum(step * rng.standard_normal(length)) + 0.002 * np.sin(2 * np.pi * t / 50)
 
 
+def _cumsum_fixed_order(x, block: int = 4096):
+    """cumsum of a 1-D device tensor with one fixed order of additions: rows of `block` samples are scanned on
+    the device (the per-row scan), the row totals on the host (numpy, sequential).  A device scan over the whole
+    1-D tensor chains its blocks' partial sums in whichever order they finish (decoupled look-back), so its
+    rounding, and with it the series, differed from run to run."""
+    import torch
+    length = x.numel()
+    pad = (-length) % block
+    if pad:
+        x = torch.cat([x, x.new_zeros(pad)])
+    rows = torch.cumsum(x.view(-1, block), 1)
+    totals = rows[:, -1].cpu().numpy()
+    before = np.concatenate([[0.0], np.cumsum(totals)[:-1]])
+    rows += torch.from_numpy(before).to(x.device)[:, None]
+    return rows.view(-1)[:length]
+
+
 def random_walk_torch(length: int, seed: int, device, dtype=None, step: float = 1e-4):
-    """Same generator shape built directly in HBM (bench: inputs resident on device)."""
+    """Same generator shape built directly in HBM (bench: inputs resident on device); the same length, seed and
+    dtype give the same samples bit for bit in every run."""
     import torch
     dtype = dtype or torch.float64
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     noise = torch.randn(length, generator=g, device=device, dtype=torch.float64)
     t = torch.arange(length, device=device, dtype=torch.float64)
-    x = 1.1 + torch.cumsum(step * noise, 0) + 0.002 * torch.sin(2 * np.pi * t / 50)
+    x = 1.1 + _cumsum_fixed_order(step * noise) + 0.002 * torch.sin(2 * np.pi * t / 50)
     return x.to(dtype)
 
 

@@ -11,8 +11,8 @@
 #   smoke                    __graft_entry__.smoke()
 #   bench=<cfg>[,<args>]     python bench.py --config <cfg> --steps 100 --warmup 20 --no-cpu-baseline <args>
 #                            (args comma-separated), line bench_<cfg>.json
-#   benchc=<cfg>[,<args>]    the same with the CPU baseline (1 core + the job's cores) in the line
-#   default                  python bench.py (the driver's default line, CPU baseline included)
+#   benchc=<cfg>[,<args>]    the same with --full: the CPU baseline (1 core + the job's cores) and this run's PMC traffic
+#   default                  python bench.py --full (the default line, CPU baseline and PMC traffic included)
 #   prof=<cfg>[,<algo>[,<variant>[,<key suffix>[,<extra bench args, + for spaces>]]]]
 #                            rocprofv3 kernel trace + stats, then FETCH_SIZE and WRITE_SIZE in their own
 #                            passes (scripts/gpu_profile.sh), parsed by scripts/parse_prof.py
@@ -64,9 +64,9 @@ for step in "$@"; do
         cat $O/smoke.log
         ;;
     bench|benchc)
-        # benchc: the same line with the CPU baseline beside it (1 core + the job's cores, the closing check)
+        # benchc: the same line as a --full run, the CPU baseline beside it (1 core + the job's cores, the closing check)
         cpuflag="--no-cpu-baseline"
-        [ "$key" = "benchc" ] && cpuflag=""
+        [ "$key" = "benchc" ] && cpuflag="--full"
         cfg=${val%%,*}
         extra=""
         [ "$cfg" != "$val" ] && extra=${val#*,}
@@ -79,7 +79,7 @@ import json; d=json.loads(open('$bf.json').read().strip().splitlines()[-1])
 print('$cfg', '$extra', d['config'].get('algorithm'), '%.4f ms'%d['ms_per_step'], '%.4g win/s'%d['value'], 'frac %.3f'%d['roofline']['frac'])"
         ;;
     default)
-        run 400 $O/bench_default.json $O/bench_default.err python bench.py
+        run 400 $O/bench_default.json $O/bench_default.err python bench.py --full
         cat $O/bench_default.json
         ;;
     prof)

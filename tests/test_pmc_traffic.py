@@ -49,7 +49,8 @@ def test_run_pmc_child_command(monkeypatch):
         return {"hbm_bytes_per_launch": 1.0}
 
     monkeypatch.setattr(pmc_traffic, "collect", fake)
-    argv = ["--config", "c3", "--steps", "50", "--warmup=4", "--variant", "8", "--cpu-seconds", "3", "--pmc", "on"]
+    argv = ["--full", "--config", "c3", "--steps", "50", "--warmup=4", "--dump-outputs", "dumped", "--variant", "8",
+            "--cpu-seconds", "3", "--pmc", "on"]
     args = bench.parse(argv)
     assert bench.run_pmc(args, argv) == {"hbm_bytes_per_launch": 1.0}
     cmd = seen["cmd"]
@@ -60,11 +61,14 @@ def test_run_pmc_child_command(monkeypatch):
     assert seen["key"] == "c3_v8"
 
 
-@pytest.mark.parametrize("argv,env,want", [([], {}, True), (["--no-cpu-baseline"], {}, False),
+@pytest.mark.parametrize("argv,env,want", [(["--full"], {}, True), (["--full", "--no-cpu-baseline"], {}, False),
                                            (["--no-cpu-baseline", "--pmc", "on"], {}, True),
-                                           (["--pmc", "off"], {}, False), ([], {"WSP_BENCH_PMC_CHILD": "1"}, False),
-                                           (["--emulate-shard", "1/8"], {}, False)])
+                                           (["--full", "--pmc", "off"], {}, False),
+                                           (["--full"], {"WSP_BENCH_PMC_CHILD": "1"}, False),
+                                           (["--full", "--emulate-shard", "1/8"], {}, False),
+                                           ([], {}, False), (["--steps", "20", "--warmup", "5"], {}, False)])
 def test_want_pmc(monkeypatch, argv, env, want):
+    """The PMC passes belong to a --full run (or an explicit --pmc on); a plain run never starts them."""
     monkeypatch.delenv("WSP_BENCH_PMC_CHILD", raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
