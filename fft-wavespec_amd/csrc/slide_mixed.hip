@@ -108,7 +108,8 @@ __device__ __forceinline__ void mix_task(MixP m, int c, int64_t task, d2 *lds, c
     constexpr int N = 1 << LOG2N, M = N / 2, B = LOG2N <= 10 ? BS : 4, NT = M / B, P = kMixNT / NT, REC = Rec<NF>::n,
                   NM = (NF - 1) / 2;
     constexpr int CH = N / 4 < 128 ? 128 : (N / 4 > kSlideRMax ? kSlideRMax : N / 4);
-    static_assert(P * N <= 4096 && CH * REC / 2 <= N && P * NT == kMixNT, "sub-workgroup geometry");
+    // a sub-workgroup's FFT buffer holds its staged uniforms and, behind them, the missing-sample flag and count
+    static_assert(P * N <= 4096 && CH * REC + kMissInts <= 2 * N && P * NT == kMixNT, "sub-workgroup geometry");
     // sub-workgroups are whole waves: the index (and the segment lookups below) are wave-uniform
     const int sub = __builtin_amdgcn_readfirstlane(threadIdx.x / NT);
     int t = threadIdx.x % NT;
@@ -139,11 +140,12 @@ __device__ __forceinline__ void mix_task(MixP m, int c, int64_t task, d2 *lds, c
     const T *__restrict__ x = static_cast<const T *>(ser) + w0;
     const d2 *__restrict__ hwin = omega + NF * M;
     const d2 *__restrict__ mod = omega + (NF + 1) * M;  // [NM][N] e^{-j m th i}
-    const double lvl = (DETREND == kDetrendMean && on) ? (double)x[0] : 0.0;
+    const double lvl = (DETREND == kDetrendMean && on) ? slide_level(x, N) : 0.0;  // the segment's level (slide_kernel)
 
     // ---- seeds: Y_m = FFT_N((x[w0 + i] - L) e^{-j m th i}) (seed_ffts), trackers of this thread's bins
     d2 om[B][NF], tr[B][NF];
     double sum = 0.0;
+    int nbad = 0;  // missing samples (slide_bad) among the seed window's samples this thread loads
 #pragma unroll
     for (int mm = 0; mm <= NM; ++mm) {
         if constexpr (SR) {  // register passes (default): the inputs straight from global memory into registers
@@ -151,13 +153,15 @@ __device__ __forceinline__ void mix_task(MixP m, int c, int64_t task, d2 *lds, c
 #pragma unroll
             for (int r = 0; r < N / NT; ++r) {
                 const int i = t + NT * r;
-                const double xi = on ? (double)x[i] - lvl : 0.0;
+                const double xr = on ? (double)x[i] : 0.0, xi = on ? slide_cen(xr, lvl) : 0.0;
+                if (mm == 0) nbad += slide_bad(xr) ? 1 : 0;
                 a[r] = mm == 0 ? d2{xi, 0.0} : xi * mod[(mm - 1) * N + i];
             }
             fft_reg_sub<LOG2N, NT, 4096 / N>(a, buf, twq, t);
         } else {  // mode 5 (ablation): the round-4 form, inputs staged in LDS and radix-4 passes through LDS
             for (int i = t; i < N; i += NT) {
-                const double xi = on ? (double)x[i] - lvl : 0.0;
+                const double xr = on ? (double)x[i] : 0.0, xi = on ? slide_cen(xr, lvl) : 0.0;
+                if (mm == 0) nbad += slide_bad(xr) ? 1 : 0;
                 buf[i] = mm == 0 ? d2{xi, 0.0} : xi * mod[(mm - 1) * N + i];
             }
             __syncthreads();
@@ -201,10 +205,16 @@ __device__ __forceinline__ void mix_task(MixP m, int c, int64_t task, d2 *lds, c
         __builtin_amdgcn_make_buffer_rsrc(static_cast<T *>(outp) + w0 * M, (short)0, 0x7fffffff, 0x00020000);
     uint32_t ob = (uint32_t)(2 * t * (int)sizeof(T));
     double *u = reinterpret_cast<double *>(buf);
+    // missing samples, per sub-workgroup as in slide_kernel: a flag the staging raises and the seed window's count
+    // behind the uniforms; the barriers are the workgroup's
+    int *mi = reinterpret_cast<int *>(u + CH * REC);
+    if (t < kMissInts) mi[t] = 0;  // the seeds ended after a barrier: buf is free
+    __syncthreads();
+    if (nbad) atomicAdd(&mi[1], nbad);
     for (int c0 = 0; c0 < maxlen; c0 += CH) {
         const int clen = maxlen - c0 < CH ? maxlen - c0 : CH;
         if (c0) __syncthreads();
-        stage_uniforms<T, NF, N>(ua, x, lvl, c0, clen < len - c0 ? clen : len - c0, len, u, t, NT);
+        stage_uniforms<T, NF, N>(ua, x, lvl, c0, clen < len - c0 ? clen : len - c0, len, u, nullptr, mi, t, NT);
         __syncthreads();
         const int act = len - c0 < clen ? (len - c0 > 0 ? len - c0 : 0) : clen;  // this sub-workgroup's windows
 #pragma unroll 1
@@ -242,6 +252,10 @@ __device__ __forceinline__ void mix_task(MixP m, int c, int64_t task, d2 *lds, c
             if (c0 + st + 1 < len) slide_step<B, NF, DETREND>(tr, om, u + st * REC, sum);
         }
     }
+    // cold, never on ordinary data: NaN rows over the windows that hold a missing sample (slide_kernel)
+    const int miss0 = __builtin_amdgcn_readfirstlane(mi[1]);
+    if (__builtin_amdgcn_readfirstlane(mi[0] | miss0) != 0)
+        missing_rows<T, N, B, NT>(x, len, miss0, static_cast<T *>(outp) + w0 * M, t, wt, orc);
     __syncthreads();  // the staged uniforms' reads before the next task's writes
 }
 

@@ -27,7 +27,8 @@
 // Y_m = FFT_N(x[w0 + i] e^{-j m th i}) in LDS (radix-4 Stockham, quarter twiddle table in LDS) gives
 // S(k/N + m phi) = Y_m[k] and S(k/N - m phi) = conj(Y_m[N-k]).  The per-step uniforms
 // (u_0, u_1, u_2, x[w+N] - x[w]) are staged in LDS a chunk at a time and read by broadcast.
-// With the mean detrend the trackers follow the samples minus the segment's first sample.
+// With the mean detrend the trackers follow the samples minus the segment's level (slide_level: the median of
+// three samples of its first window).
 // Rounding: a tracker's error grows at most linearly with the segment length (<= 256 steps by
 // default: ~3e-14 of its own magnitude); the parity bars are BASELINE.md 2's (tests/test_gpu_slide.py,
 // tests/test_gpu_fullgrid.py, the CPU model tests/test_slide_model.py).
@@ -55,6 +56,86 @@ constexpr int kSlideRMax = 512;  // most steps whose uniforms are staged in LDS 
 template <int NF> struct Rec { static constexpr int n = NF + 1; };  // [u0, (u1r, u1i), (u2r, u2i), d]
 
 __device__ __forceinline__ d2 cmul(d2 a, d2 b) { return d2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+
+// Window isolation (include/mtbridge.h, wsp_plan_set_algorithm; tests/test_gpu_isolation.py).  A tracker carries
+// every sample it has seen until the segment ends, so a sample it cannot carry -- NaN, Inf, or a magnitude whose
+// sums and squares overflow (MQL5's EMPTY_VALUE = DBL_MAX marks a missing bar) -- is MISSING, not data: it enters
+// and leaves the trackers as the level (zero after centring; the same memory word is read both times, so the two
+// substitutions agree) and is counted while it is inside the window: a window with a non-zero count ends as a
+// NaN row (top-k: missing_slot in every slot).  The slide loops do not know of it: the seed counts its window, the
+// staging raises a flag when a missing sample enters or leaves, and only then (never on ordinary data) the same
+// threads walk the segment again after its last window -- the count follows from the samples that enter and leave
+// -- and overwrite the rows of the windows that hold one.
+constexpr double kSlideBig = 1e140;  // N kSlideBig and its square are finite for every N here
+__device__ __forceinline__ bool slide_bad(double v) { return !(fabs(v) <= kSlideBig); }
+__device__ __forceinline__ double slide_cen(double v, double lvl) { return slide_bad(v) ? 0.0 : v - lvl; }
+// The mean path's level L: the median of the segment's first window's first, middle and last sample, so that one
+// bad tick cannot set it (of fewer usable samples the first; 0 with none).  Any finite L gives the same spectra in
+// exact arithmetic; L near the window's mean keeps |mean - L| H_k from cancelling against the trackers.
+template <typename T> __device__ __forceinline__ double slide_level(const T *__restrict__ x, int n) {
+    const double a = (double)x[0], b = (double)x[n / 2], c = (double)x[n - 1];
+    const bool ba = slide_bad(a), bb = slide_bad(b), bc = slide_bad(c);
+    if (!(ba || bb || bc)) return fmax(fmin(a, b), fmin(fmax(a, b), c));
+    return !ba ? a : (!bb ? b : (!bc ? c : 0.0));
+}
+// Beside a segment's staged uniforms: [0] set when a missing sample enters or leaves one of its windows, [1] the
+// seed window's count of them.
+constexpr int kMissInts = 2;
+// The count after step st: sample st + N enters, sample st leaves (uniform loads; cold).
+template <typename T, int N> __device__ __forceinline__ int miss_step(const T *__restrict__ x, int st, int miss) {
+    const int d = (slide_bad((double)x[st + N]) ? 1 : 0) - (slide_bad((double)x[st]) ? 1 : 0);
+    return __builtin_amdgcn_readfirstlane(miss + d);
+}
+// The top-k record of a window that holds a missing sample: every slot {bin -1, NaN, NaN, NaN} (an empty slot of an
+// ordinary window is {-1, -1, 0, 0}); lanes s, s + 64, ... of the wave write slot s.
+typedef double d4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ d4 missing_slot() {
+    const double q = __builtin_nan("");
+    return d4{-1.0, q, q, q};
+}
+__device__ __forceinline__ void missing_record(double *rec, int k, int lane) {
+    for (int s = lane; s < k; s += 64) *reinterpret_cast<d4 *>(rec + 4 * s) = missing_slot();
+}
+// Cold pass of a scan wave after its segment of `len` windows, whose records (rec: the first window's) it has
+// written: the records of the windows that hold a missing sample are overwritten (the same wave's later stores to
+// the same addresses).  miss: the count in the segment's first window.
+template <int N>
+__device__ __forceinline__ void missing_records(double *rec, int k, int lane, int miss, const double *__restrict__ x, int len) {
+    for (int st = 0; st < len; ++st) {
+        if (miss != 0) missing_record(rec + (int64_t)st * (4 * k), k, lane);
+        if (st + 1 < len) miss = miss_step<double, N>(x, st, miss);
+    }
+}
+// The same for power rows (slide_kernel, the mixed launch): thread t of NT, B bins each, overwrites its pairs of the
+// rows of the windows that hold a missing sample with NaN -- the same thread, addresses and store kind as the slide
+// loop's rows (written through: orc based at the segment's first row; else plain stores from row0).
+template <typename T, int N, int B, int NT>
+__device__ __forceinline__ void missing_rows(const T *__restrict__ x, int len, int miss, T *row0, int t, bool wt,
+                                             __amdgpu_buffer_rsrc_t orc) {
+    typedef T v2t __attribute__((ext_vector_type(2)));
+    const T q = (T)__builtin_nan("");
+    const v2t pv = v2t{q, q};
+    for (int st = 0; st < len; ++st) {
+        if (miss != 0) {
+#pragma unroll
+            for (int qq = 0; qq < B / 2; ++qq) {
+                const int64_t e = (int64_t)st * (N / 2) + 2 * t + 2 * NT * qq;  // element within the segment
+                if (wt) {
+                    if constexpr (sizeof(T) == 8) {
+                        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, pv), orc, (int)(e * sizeof(T)), 0, 16);
+                    } else {
+                        typedef unsigned u2 __attribute__((ext_vector_type(2)));
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, pv), orc, (int)(e * sizeof(T)), 0, 16);
+                    }
+                } else {
+                    *reinterpret_cast<v2t *>(row0 + e) = pv;
+                }
+            }
+        }
+        if (st + 1 < len) miss = miss_step<T, N>(x, st, miss);
+    }
+}
 
 // In-place natural-order complex FFT of N points in LDS: Stockham DIT, one radix-2 stage first when
 // log2 N is odd, then radix 4; NT threads.  twl[k] = W_N^k for k < N/4 (LDS, or the global table at
@@ -190,10 +271,11 @@ __device__ __forceinline__ void fft_reg_sub(d2 (&a)[(1 << LOG2N) / NT], d2 *buf,
 template <int NT> __device__ __forceinline__ int kbin_of(int t, int b) { return 2 * (t + NT * (b >> 1)) + (b & 1); }
 
 // The segment's seeds: Y_m = FFT_N((x[w0 + i] - L) e^{-j m th i}), m = 0 .. (NF-1)/2, in LDS; pick(m, s_m, Y)
-// takes what it needs from each transform (every thread calls it between the transform's barriers).
+// takes what it needs from each transform (every thread calls it between the transform's barriers).  nbad: the
+// missing samples (slide_bad) among the ones this thread loaded.
 template <typename T, int LOG2N, int NF, int DETREND, int NT, typename PICK>
 __device__ __forceinline__ void seed_ffts(const SlideArgs &a, const T *__restrict__ x, double lvl, d2 *lds, d2 *twq,
-                                          PICK pick) {
+                                          int &nbad, PICK pick) {
     constexpr int N = 1 << LOG2N, M = N / 2, NM = (NF - 1) / 2;
     constexpr bool TWL = N <= 4096;  // the quarter twiddle table fits LDS beside the FFT buffer
     const int t = threadIdx.x;
@@ -215,13 +297,15 @@ __device__ __forceinline__ void seed_ffts(const SlideArgs &a, const T *__restric
 #pragma unroll
             for (int r = 0; r < N / NT; ++r) {
                 const int i = t + NT * r;
-                const double xi = (double)x[i] - lvl;
+                const double xr = (double)x[i], xi = slide_cen(xr, lvl);
+                if (m == 0) nbad += slide_bad(xr) ? 1 : 0;
                 v[r] = m == 0 ? d2{xi, 0.0} : xi * mod[(m - 1) * N + i];
             }
             fft_reg_sub<LOG2N, NT, 1>(v, lds, twl, t);
         } else {
             for (int i = t; i < N; i += NT) {
-                const double xi = (double)x[i] - lvl;
+                const double xr = (double)x[i], xi = slide_cen(xr, lvl);
+                if (m == 0) nbad += slide_bad(xr) ? 1 : 0;
                 lds[i] = m == 0 ? d2{xi, 0.0} : xi * mod[(m - 1) * N + i];
             }
             __syncthreads();
@@ -233,14 +317,20 @@ __device__ __forceinline__ void seed_ffts(const SlideArgs &a, const T *__restric
 }
 
 // Per-step uniforms of steps c0 .. c0 + clen - 1 into u[st * REC]: u_m = s_m (x[w+N] e^{-j m th} - x[w]),
-// d = x[w+N] - x[w] (samples minus the segment's level L); no step after the segment's last window.
+// d = x[w+N] - x[w] (samples minus the segment's level L, a missing sample as L); no step after the segment's last
+// window.  *flag is set when a staged sample is missing; dm (the chained seeds; else null): dm[st] = step st's change
+// of the window's count of them.
 template <typename T, int NF, int N>
 __device__ __forceinline__ void stage_uniforms(const SlideArgs &a, const T *__restrict__ x, double lvl, int c0,
-                                               int clen, int len, double *u, int t, int nt) {
+                                               int clen, int len, double *u, int *dm, int *flag, int t, int nt) {
     constexpr int REC = Rec<NF>::n;
     for (int st = t; st < clen; st += nt) {
         if (c0 + st + 1 >= len) break;
-        const double xw = (double)x[c0 + st] - lvl, xn = (double)x[c0 + st + N] - lvl;
+        const double rw = (double)x[c0 + st], rn = (double)x[c0 + st + N];
+        const bool bw = slide_bad(rw), bn = slide_bad(rn);
+        const double xw = bw ? 0.0 : rw - lvl, xn = bn ? 0.0 : rn - lvl;
+        if (dm) dm[st] = (bn ? 1 : 0) - (bw ? 1 : 0);
+        if (bw || bn) *flag = 1;
         double *r = u + st * REC;
         r[0] = a.s0 * (xn - xw);
         if constexpr (NF >= 3) {
@@ -308,7 +398,8 @@ __global__ __launch_bounds__((1 << LOG2N) / (2 * slide_b<LOG2N>()),
     // per-step uniforms staged CH steps at a time: N/4 clamped to [128, 512], so that small windows keep
     // 4 single-/two-wave workgroups per SIMD (LDS: FFT buffer + quarter twiddles + uniforms)
     constexpr int CH = N / 4 < 128 ? 128 : (N / 4 > kSlideRMax ? kSlideRMax : N / 4);
-    constexpr int LDS2 = (N > CH * REC / 2) ? N : CH * REC / 2;
+    constexpr int UD2 = (CH * REC + kMissInts) / 2 + 1;  // uniforms + the missing-sample flag and count, in d2
+    constexpr int LDS2 = (N > UD2) ? N : UD2;  // = N: they ride in the FFT buffer's slack, no LDS added
     constexpr bool TWL = N <= 4096;  // the quarter twiddle table fits LDS beside the FFT buffer
     __shared__ d2 lds[LDS2];
     __shared__ d2 twq[TWL ? N / 4 : 1];
@@ -331,13 +422,15 @@ __global__ __launch_bounds__((1 << LOG2N) / (2 * slide_b<LOG2N>()),
     }
 
     d2 om[B][NF], tr[B][NF];
-    // mean detrend: the trackers follow x - L, L = the segment's first sample, and the output subtracts
-    // (mean - L) H_k: X_w - mean_w H = X(x - L) - (mean_w - L) H.  Centring keeps the ~N x price level
-    // out of the trackers near DC (20x smaller rounding at bins 0-2, tests/test_slide_model.py).
-    const double lvl = DETREND == kDetrendMean ? (double)x[0] : 0.0;
+    // mean detrend: the trackers follow x - L, L = the level of the segment's first window (slide_level: a median
+    // of three of its samples), and the output subtracts (mean - L) H_k: X_w - mean_w H = X(x - L) - (mean_w - L) H.
+    // Centring keeps the ~N x price level out of the trackers near DC (20x smaller rounding at bins 0-2,
+    // tests/test_slide_model.py).
+    const double lvl = DETREND == kDetrendMean ? slide_level(x, N) : 0.0;
 
     double sum0 = 0.0;
-    seed_ffts<T, LOG2N, NF, DETREND, NT>(a, x, lvl, lds, twq, [&](int m, double s, const d2 *y) {
+    int nbad = 0;
+    seed_ffts<T, LOG2N, NF, DETREND, NT>(a, x, lvl, lds, twq, nbad, [&](int m, double s, const d2 *y) {
 #pragma unroll
         for (int b = 0; b < B; ++b) {
             const int k = kbin(t, b);
@@ -373,10 +466,15 @@ __global__ __launch_bounds__((1 << LOG2N) / (2 * slide_b<LOG2N>()),
         __builtin_amdgcn_make_buffer_rsrc(static_cast<T *>(sg.out) + sg.w0 * M, (short)0, 0x7fffffff, 0x00020000);
     uint32_t ob = (uint32_t)(2 * t * (int)sizeof(T));
     double *u = reinterpret_cast<double *>(lds);
+    // missing samples (slide_bad): a flag the staging raises and the seed window's count, behind the uniforms
+    int *mi = reinterpret_cast<int *>(u + CH * REC);
+    if (t < kMissInts) mi[t] = 0;  // the seeds ended after a barrier: lds is free
+    __syncthreads();
+    if (nbad) atomicAdd(&mi[1], nbad);
     for (int c0 = 0; c0 < len; c0 += CH) {
         const int clen = len - c0 < CH ? len - c0 : CH;
         if (c0) __syncthreads();  // the previous chunk's reads are done
-        stage_uniforms<T, NF, N>(a, x, lvl, c0, clen, len, u, t, NT);
+        stage_uniforms<T, NF, N>(a, x, lvl, c0, clen, len, u, nullptr, mi, t, NT);
         __syncthreads();
 
         // ---- slide
@@ -418,6 +516,11 @@ __global__ __launch_bounds__((1 << LOG2N) / (2 * slide_b<LOG2N>()),
             if (c0 + st + 1 < len) slide_step<B, NF, DETREND>(tr, om, u + st * REC, sum);
         }
     }
+    // cold, never on ordinary data: NaN rows over the windows that hold a missing sample (mi: written before the
+    // last chunk's barrier)
+    const int miss0 = __builtin_amdgcn_readfirstlane(mi[1]);
+    if (__builtin_amdgcn_readfirstlane(mi[0] | miss0) != 0)
+        missing_rows<T, N, B, NT>(x, len, miss0, static_cast<T *>(sg.out) + sg.w0 * M, t, wt, orc);
     if (trc) trc[3] = wall_clock64();
 }
 
@@ -439,10 +542,11 @@ __global__ __launch_bounds__(seed_nt<LOG2N>()) void slide_seed_kernel(SlideArgs 
     const int64_t w0 = (int64_t)blockIdx.x * a.seg;
     if (w0 >= a.n_windows) return;
     const T *__restrict__ x = static_cast<const T *>(a.series) + w0;
-    const double lvl = DETREND == kDetrendMean ? (double)x[0] : 0.0;
+    const double lvl = DETREND == kDetrendMean ? slide_level(x, N) : 0.0;
     d2 *__restrict__ ws = static_cast<d2 *>(a.ws) + blockIdx.x * slide_topk_seed_stride(NF, a.span);
     const int span = a.span, kmin = a.kmin;
-    seed_ffts<T, LOG2N, NF, DETREND, NT>(a, x, lvl, lds, twq, [&](int m, double s, const d2 *y) {
+    int nbad = 0;
+    seed_ffts<T, LOG2N, NF, DETREND, NT>(a, x, lvl, lds, twq, nbad, [&](int m, double s, const d2 *y) {
         for (int j = t; j < span; j += NT) {
             const int k = kmin + j;
             if (m == 0) {
@@ -455,6 +559,13 @@ __global__ __launch_bounds__(seed_nt<LOG2N>()) void slide_seed_kernel(SlideArgs 
         }
         if (m == 0 && t == 0) ws[NF * span] = d2{y[0].x, lvl};
     });
+    // the seed window's count of missing samples (the transforms ended after a barrier: lds is free)
+    int *cnt = reinterpret_cast<int *>(lds);
+    if (t == 0) cnt[0] = 0;
+    __syncthreads();
+    if (nbad) atomicAdd(cnt, nbad);
+    __syncthreads();
+    if (t == 0) ws[NF * span + 1] = d2{(double)cnt[0], 0.0};
 }
 
 // The same seeds by the register-resident workgroup FFT (wg::wg_fft: N/16 threads, 16 points each, radix-16
@@ -477,6 +588,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
     constexpr int N = 1 << LOG2N, M = N / 2, TP = G::TP, NM = (NF - 1) / 2, R = wg::last_radix<LOG2N>();
     constexpr int REC = Rec<NF>::n;  // JB: band bins per thread, span <= JB TP (launch_topk_t)
     __shared__ core::cpx<double> lds[G::SLOT];
+    __shared__ int seed_miss;
     const int t = threadIdx.x;
     const int chain = a.seed_chain > 1 ? a.seed_chain : 1;
     const int64_t sg0 = (int64_t)blockIdx.x * chain;  // this workgroup's first segment
@@ -493,7 +605,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
     const double *__restrict__ x = static_cast<const double *>(a.series) + w0;
     const core::cpx<double> *__restrict__ tw = static_cast<const core::cpx<double> *>(a.twiddle);
     const d2 *__restrict__ mod = static_cast<const d2 *>(a.omega) + (NF + 1) * M;  // [NM][N] e^{-j m th i}
-    const double lvl = DETREND == kDetrendMean ? x[0] : 0.0;
+    const double lvl = DETREND == kDetrendMean ? slide_level(x, N) : 0.0;
     const int64_t stride = slide_topk_seed_stride(NF, a.span);
     d2 *__restrict__ ws = static_cast<d2 *>(a.ws) + sg0 * stride;
     const int span = a.span, kmin = a.kmin;
@@ -518,8 +630,15 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
     d2 trk[JB][NF];  // the chain's trackers of bins kmin + t + TP i
     double sum = 0.0;
     double xs[16];
+    // missing samples (slide_bad) among this thread's, summed in seed_miss between the first transform's barriers
+    int nbad = 0, miss = 0;
+    if (t == 0) seed_miss = 0;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) xs[r] = x[t + TP * r] - lvl;
+    for (int r = 0; r < 16; ++r) {
+        const double xr = x[t + TP * r];
+        nbad += slide_bad(xr) ? 1 : 0;
+        xs[r] = slide_cen(xr, lvl);
+    }
 #pragma unroll
     for (int m = 0; m <= NM; ++m) {
         core::cpx<double> v[16];
@@ -533,6 +652,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
             }
         }
         wg::wg_fft<double, LOG2N>(v, lds, t, tw, LOG2N);  // ends after a barrier: lds is free
+        if (m == 0 && nbad) atomicAdd(&seed_miss, nbad);  // zeroed before the transform's barriers, read after the next
         // v[q R + r] = Y[b + (N/R) r], b = t + TP q: natural order into lds
 #pragma unroll
         for (int q = 0; q < 16 / R; ++q)
@@ -559,7 +679,11 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
         }
         if (m == 0) {
             sum = lds[0].re;  // sum of x - L (mean path)
-            if (t == 0) wst(ws + NF * span, d2{sum, lvl});  // and L
+            miss = __builtin_amdgcn_readfirstlane(seed_miss);
+            if (t == 0) {
+                wst(ws + NF * span, d2{sum, lvl});  // and L
+                wst(ws + NF * span + 1, d2{(double)miss, 0.0});  // and the seed window's count of missing samples
+            }
         }
         __syncthreads();  // the band reads before the next transform's exchanges
         if (trc) trc[2 + (m > 0)] = wall_clock64();
@@ -586,8 +710,9 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
     const int64_t last = a.n_windows - 1 - w0;  // no step past the batch's last window
     const int nsteps = (int)((chain - 1) * seg < last ? (chain - 1) * seg : last);
     double *u = reinterpret_cast<double *>(lds);
-    static_assert(256 * REC <= G::SLOT * 2, "a chain's uniforms fit the FFT's LDS");
-    stage_uniforms<double, NF, N>(a, x, lvl, 0, nsteps, nsteps + 1, u, t, TP);
+    int *dm = reinterpret_cast<int *>(u + 256 * REC);  // each step's change of the count, then the (unused) flag
+    static_assert(256 * REC + (256 + 2) / 2 <= G::SLOT * 2, "a chain's uniforms fit the FFT's LDS");
+    stage_uniforms<double, NF, N>(a, x, lvl, 0, nsteps, nsteps + 1, u, dm, dm + 256, t, TP);
     __syncthreads();
     auto put = [&](int g) {
         d2 *__restrict__ wsg = ws + g * stride;
@@ -598,7 +723,10 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
 #pragma unroll
             for (int f = 0; f < NF; ++f) wst(wsg + f * span + j, trk[i][f]);
         }
-        if (t == 0) wst(wsg + NF * span, d2{sum, lvl});  // the chain's level L (the scan's uniforms follow x - L)
+        if (t == 0) {
+            wst(wsg + NF * span, d2{sum, lvl});  // the chain's level L (the scan's uniforms follow x - L)
+            wst(wsg + NF * span + 1, d2{(double)miss, 0.0});
+        }
     };
     for (int g = 1; g < chain; ++g) {
         const int64_t wsg0 = g * seg;  // this segment's first window, relative to w0
@@ -608,6 +736,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void slide_seed_r_kernel(SlideAr
         const int st1 = (int)wsg0;
 #pragma unroll 8
         for (int st = st1 - (int)seg; st < st1; ++st) slide_step<JB, NF, DETREND>(trk, om, u + st * REC, sum);
+        for (int st = st1 - (int)seg; st < st1; ++st) miss += dm[st];
         put(g);
     }
     if (trc) trc[4] = trc[5] = wall_clock64();
@@ -621,6 +750,7 @@ template <int LOG2N, int NF, int DETREND, int NB>
 __global__ __launch_bounds__(64) void slide_topk_kernel(SlideArgs a) {
     constexpr int N = 1 << LOG2N, M = N / 2, REC = Rec<NF>::n, CHT = 128;
     __shared__ double u[CHT * REC];
+    __shared__ int mi[kMissInts];  // [0]: a missing sample enters or leaves in this segment
     __shared__ core::cpx<double> xb[64 * NB];
     const int l = threadIdx.x;
     const int64_t w0 = (int64_t)blockIdx.x * a.seg;
@@ -646,11 +776,13 @@ __global__ __launch_bounds__(64) void slide_topk_kernel(SlideArgs a) {
     const d2 sl = ws[NF * span];
     double sum = sl.x;
     const double lvl = sl.y;
+    const int miss0 = __builtin_amdgcn_readfirstlane((int)ws[NF * span + 1].x);  // missing samples in the seed window
+    if (l == 0) mi[0] = 0;
     double *__restrict__ rec = static_cast<double *>(a.out) + w0 * (int64_t)(4 * a.topk);
     for (int c0 = 0; c0 < len; c0 += CHT) {
         const int clen = len - c0 < CHT ? len - c0 : CHT;
-        if (c0) __syncthreads();
-        stage_uniforms<double, NF, N>(a, x, lvl, c0, clen, len, u, l, 64);
+        __syncthreads();
+        stage_uniforms<double, NF, N>(a, x, lvl, c0, clen, len, u, nullptr, mi, l, 64);
         __syncthreads();
 #pragma unroll 1
         for (int st = 0; st < clen; ++st) {
@@ -670,6 +802,9 @@ __global__ __launch_bounds__(64) void slide_topk_kernel(SlideArgs a) {
             if (c0 + st + 1 < len) slide_step<NB, NF, DETREND>(tr, om, u + st * REC, sum);
         }
     }
+    // cold, never on ordinary data: the records of the windows that hold a missing sample
+    if (__builtin_amdgcn_readfirstlane(mi[0] | miss0) != 0)
+        missing_records<N>(static_cast<double *>(a.out) + w0 * (int64_t)(4 * a.topk), a.topk, l, miss0, x, len);
 }
 
 // ---- the same records by a transposed scan (k <= 8): lane per window instead of a wave per window.
@@ -745,6 +880,7 @@ __global__ __launch_bounds__(64) void slide_topk_t_kernel(SlideArgs a) {
     constexpr int N = 1 << LOG2N, M = N / 2, REC = Rec<NF>::n, CHT = 128, LPW = 64 / WB, K = kTopkT;
     constexpr int kEmpty = 0x7fffffff;  // bin of an empty slot: sorts after every real bin
     __shared__ double u[CHT * REC];
+    __shared__ int mi[kMissInts];  // [0]: a missing sample enters or leaves in this segment
     extern __shared__ d2 xs[];  // [WB][span | 1], sized at launch: the LDS a wave holds sets the occupancy
     const int l = threadIdx.x;
     const int64_t w0 = (int64_t)blockIdx.x * a.seg;
@@ -770,6 +906,8 @@ __global__ __launch_bounds__(64) void slide_topk_t_kernel(SlideArgs a) {
     const d2 sl = ws[NF * span];
     double sum = sl.x;
     const double lvl = sl.y;
+    const int miss0 = __builtin_amdgcn_readfirstlane((int)ws[NF * span + 1].x);  // missing samples in the seed window
+    if (l == 0) mi[0] = 0;
     // the scan's lane roles: window mw of the staged batch, band part mq: bins mq, mq + LPW, ...
     const int mw = l % WB, mq = l / WB;
     double *__restrict__ rec = static_cast<double *>(a.out) + w0 * (int64_t)(4 * a.topk);
@@ -781,8 +919,8 @@ __global__ __launch_bounds__(64) void slide_topk_t_kernel(SlideArgs a) {
     int *cj = reinterpret_cast<int *>(cp + (kCand + 1) * 64);
     for (int c0 = 0; c0 < len; c0 += CHT) {
         const int clen = len - c0 < CHT ? len - c0 : CHT;
-        if (c0) __syncthreads();
-        stage_uniforms<double, NF, N>(a, x, lvl, c0, clen, len, u, l, 64);
+        __syncthreads();
+        stage_uniforms<double, NF, N>(a, x, lvl, c0, clen, len, u, nullptr, mi, l, 64);
         __syncthreads();
 #pragma unroll 1
         for (int st = 0; st < clen; ++st) {
@@ -880,7 +1018,6 @@ __global__ __launch_bounds__(64) void slide_topk_t_kernel(SlideArgs a) {
                         const bool real = bs != kEmpty;
                         d2 X = d2{0.0, 0.0};
                         if (real) X = xs[mw * sp + bs];
-                        typedef double d4 __attribute__((ext_vector_type(4)));
                         *reinterpret_cast<d4 *>(o + 4 * s) =
                             real ? d4{(double)(kmin + bs), ps, X.x, X.y} : d4{-1.0, -1.0, 0.0, 0.0};
                     }
@@ -889,6 +1026,8 @@ __global__ __launch_bounds__(64) void slide_topk_t_kernel(SlideArgs a) {
             __syncthreads();  // the scan's reads before the next batch's writes
         }
     }
+    // cold, never on ordinary data: the records of the windows that hold a missing sample
+    if (__builtin_amdgcn_readfirstlane(mi[0] | miss0) != 0) missing_records<N>(rec, kk, l, miss0, x, len);
 }
 
 // ---- the same records by a probe threshold (default for k <= 8 and bands <= 256 bins).
@@ -913,6 +1052,7 @@ __global__ __launch_bounds__(64, (NB > 2 && LB > 2) ? 2 : LB) void slide_topk_p_
     constexpr int kEmpty = 0x7fffffff;
     static_assert(WB <= 32 && CHT % WB == 0, "one lane and one mask bit per window of a batch");
     __shared__ double u[CHT * REC];
+    __shared__ int mi[kMissInts];  // [0]: a missing sample enters or leaves in this segment
     __shared__ core::cpx<double> xb[64 * NB];  // the fallback's band
     __shared__ int win[K];                     // the fallback's winners (band index, -1 empty)
     __shared__ unsigned nm[64 * NB];           // next batch's probe bits per band bin
@@ -951,13 +1091,15 @@ __global__ __launch_bounds__(64, (NB > 2 && LB > 2) ? 2 : LB) void slide_topk_p_
     const d2 sl = ws[NF * span];
     double sum = sl.x;
     const double lvl = sl.y;
+    const int miss0 = __builtin_amdgcn_readfirstlane((int)ws[NF * span + 1].x);  // missing samples in the seed window
+    if (l == 0) mi[0] = 0;
     double *__restrict__ rec = static_cast<double *>(a.out) + w0 * (int64_t)(4 * a.topk);
     const int kk = a.topk;
     const bool probes = span >= kk;  // every window's winners are min(k, span) real bins
     for (int c0 = 0; c0 < len; c0 += CHT) {
         const int clen = len - c0 < CHT ? len - c0 : CHT;
         __syncthreads();
-        stage_uniforms<double, NF, N>(a, x, lvl, c0, clen, len, u, l, 64);
+        stage_uniforms<double, NF, N>(a, x, lvl, c0, clen, len, u, nullptr, mi, l, 64);
         __syncthreads();
 #pragma unroll 1
         for (int st = 0; st < clen; ++st) {
@@ -1062,6 +1204,8 @@ __global__ __launch_bounds__(64, (NB > 2 && LB > 2) ? 2 : LB) void slide_topk_p_
             }
         }
     }
+    // cold, never on ordinary data: the records of the windows that hold a missing sample
+    if (__builtin_amdgcn_readfirstlane(mi[0] | miss0) != 0) missing_records<N>(rec, kk, l, miss0, x, len);
     if (trs) trs[1] = wall_clock64();
 }
 

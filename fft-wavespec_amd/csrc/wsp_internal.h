@@ -204,7 +204,8 @@ int slide_mix_resident(int nf, int detrend, bool f32, int bsmall, int dev);
 // hop = 1 top-k records ([bin, power, Re, Im] x topk per window, MTB_OUT_TOPK) by the sliding DFT: the
 // band's trackers only (span <= 512), one wave per segment, the FFT kernel's one-wave scan per window.
 constexpr int kSlideTopkMaxSpan = 512;
-__host__ __device__ inline int64_t slide_topk_seed_stride(int nf, int span) { return (int64_t)nf * span + 1; }
+// per segment: [nf][span] trackers, {sum of x - L, L}, {missing samples in the seed window, 0}
+__host__ __device__ inline int64_t slide_topk_seed_stride(int nf, int span) { return (int64_t)nf * span + 2; }
 hipError_t launch_slide_topk(const SlideArgs &a, hipStream_t stream);
 
 }  // namespace wsp

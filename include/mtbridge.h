@@ -181,7 +181,11 @@ MTB_API int32_t gpu_spectral_phase_unwrap(const double *spectrum, int32_t spectr
  * MTB_DETREND_IIR.  precision: MTB_PREC_F64 or MTB_PREC_F32 (the f32 device
  * path converts the series to float on the host and results back).
  * window_len: power of two, 32..262144; above 16384 the outputs are
- * MTB_OUT_POWER and MTB_OUT_PACKED (four-step transform).  Synchronous. */
+ * MTB_OUT_POWER and MTB_OUT_PACKED (four-step transform).  Synchronous.
+ * A window's record depends on its own samples only; an eligible hop = 1 batch
+ * of at least 256 windows takes the sliding DFT (wsp_plan_set_algorithm), where
+ * a window containing a NaN, Inf or DBL_MAX (EMPTY_VALUE) sample yields an
+ * all-NaN row and the other windows are unaffected. */
 MTB_API int32_t gpu_spectrum_batch(const double *series, int32_t series_len, int32_t window_len, int32_t hop,
                                    int32_t detrend, int32_t window, int32_t trend_period, int32_t precision,
                                    int32_t output, double *out, int32_t out_cap, int32_t *out_len);
@@ -304,7 +308,22 @@ MTB_API int32_t wsp_plan_set_topk(int64_t plan, int32_t top_k, double min_period
  * at most 512 bins -- and has at least 256
  * windows, otherwise the per-window FFT.  MTB_ALGO_FFT / MTB_ALGO_SLIDE force
  * one (MTB_BAD_ARGS if the plan is not eligible for the slide).  Both produce
- * the same spectra within the parity bars. */
+ * the same spectra within the parity bars.
+ *
+ * Window isolation (tests/test_gpu_isolation.py): whichever algorithm runs, a
+ * window's record depends on that window's own window_len samples only, as
+ * with the reference's one FFT per window.  The sliding DFT carries trackers
+ * from window to window, so a sample it cannot carry -- NaN, +-Inf, or a
+ * magnitude above 1e140 such as MQL5's EMPTY_VALUE (DBL_MAX) -- is treated as
+ * missing: every window that contains it gets an all-NaN power row, or, for
+ * MTB_OUT_TOPK, a record whose every slot is {bin -1, NaN, NaN, NaN} (an empty
+ * slot of an ordinary window stays {-1, -1, 0, 0}); every other window is
+ * unaffected, within the same bars.  (The per-window FFT kernels propagate such
+ * a sample arithmetically: at least one non-finite value in a NaN / Inf
+ * window's power row, no promise for DBL_MAX.)  A finite outlier is data: the
+ * windows that contain it are exact, and the later windows of its segment
+ * carry its rounding, about 1.5e-14 of its magnitude relative to the row --
+ * inside the bars up to ~1000 x the price level. */
 #define MTB_ALGO_AUTO 0
 #define MTB_ALGO_FFT 1
 #define MTB_ALGO_SLIDE 2
@@ -335,7 +354,7 @@ MTB_API int32_t wsp_plan_set_seed_chain(int64_t plan, int32_t segments);
  * (start, loads done, FFT done, block done) at 32 b.  capacity = 0 turns it off
  * (the default).  MTB_BAD_ARGS for an unknown plan or a null buffer. */
 MTB_API int32_t wsp_plan_set_trace(int64_t plan, void *d_trace, int64_t capacity);
-/* Tuning / ablation: the kernel form, 0..8 (MTB_BAD_ARGS outside); 0 = the
+/* Tuning / ablation: the kernel form, 0..9 (MTB_BAD_ARGS outside); 0 = the
  * library's choice (default).  Same records within the parity bars either way.
  *  - hop = 1 power rows by the sliding DFT: 7 = plain stores (the default
  *    writes the rows through to memory, agent-scope sc1 stores);

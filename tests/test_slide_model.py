@@ -34,17 +34,39 @@ def slide_tables(n, window):
     return nf, sc, omega, h
 
 
+SLIDE_BIG = 1e140  # kSlideBig (sliding_core.h): a sample beyond it, NaN or Inf is missing, not data
+
+
+def slide_bad(v):
+    return ~(np.abs(v) <= SLIDE_BIG)
+
+
+def slide_level(x0, xm, xl):
+    """The mean path's level L (sliding_core.h slide_level): the median of the segment's first window's first,
+    middle and last sample, so that one bad tick cannot set it; of fewer usable samples the first, else 0."""
+    ok = [v for v in (x0, xm, xl) if not slide_bad(v)]
+    if len(ok) == 3:
+        return max(min(x0, xm), min(max(x0, xm), xl))
+    return ok[0] if ok else 0.0
+
+
 def slide_model(series, n, window, detrend, seg):
-    """Power rows of every hop = 1 window, segment by segment as the kernel runs them."""
+    """Power rows of every hop = 1 window, segment by segment as the kernel runs them: a missing sample enters
+    and leaves the trackers as the level (zero after centring) and is counted while it is inside the window;
+    a window with a non-zero count is a NaN row."""
     nf, sc, omega, h = slide_tables(n, window)
     m2, nw = n // 2, series.size - n + 1
     th = 2 * np.pi / (n - 1)
     out = np.empty((nw, m2))
     i = np.arange(n)
+    bad = slide_bad(series)
     for w0 in range(0, nw, seg):
         ln = min(seg, nw - w0)
-        lvl = series[w0] if detrend == "mean" else 0.0  # the kernel centres the mean path
-        x = series[w0:w0 + n] - lvl
+        # the kernel centres the mean path
+        lvl = slide_level(series[w0], series[w0 + n // 2], series[w0 + n - 1]) if detrend == "mean" else 0.0
+        cen = np.where(bad, 0.0, np.where(bad, 0.0, series) - lvl)
+        x = cen[w0:w0 + n]
+        cnt = int(bad[w0:w0 + n].sum())
         tr = np.empty((nf, m2), complex)
         tr[0] = sc[0] * np.fft.fft(x)[:m2]
         for m in range(1, (nf - 1) // 2 + 1):
@@ -56,9 +78,10 @@ def slide_model(series, n, window, detrend, seg):
             X = tr.sum(axis=0)
             if detrend == "mean":
                 X = X - (s / n) * h
-            out[w0 + st] = X.real ** 2 + X.imag ** 2
+            out[w0 + st] = X.real ** 2 + X.imag ** 2 if cnt == 0 else np.nan
             if st + 1 < ln:
-                xw, xn = series[w0 + st] - lvl, series[w0 + st + n] - lvl
+                xw, xn = cen[w0 + st], cen[w0 + st + n]
+                cnt += int(bad[w0 + st + n]) - int(bad[w0 + st])
                 u = np.empty(nf, complex)
                 u[0] = sc[0] * (xn - xw)
                 for m in range(1, (nf - 1) // 2 + 1):
@@ -112,6 +135,53 @@ def test_slide_model_level_shift_stress():
     kmin, kmax = oracle.band(n)
     assert oracle.rel_err(got, want) <= 1e-10
     assert oracle.inband_err(got, want, kmin, kmax) <= 1e-10
+
+
+def _split(nwin, n, c):
+    """Windows that hold sample c (hop = 1) and the rest, from c and N alone."""
+    w = np.arange(nwin)
+    dirty = (w <= c) & (c < w + n)
+    return ~dirty, dirty
+
+
+@pytest.mark.parametrize("window", ["hann", "blackman"])
+@pytest.mark.parametrize("seg", [32, 100, 600])
+def test_slide_model_outlier_on_segment_start(seg, window):
+    """+100 (~100 x the price level) on a segment's first sample, mean detrend: with the level taken from that
+    sample alone |mean - L| ~ 100 for the whole segment and the subtraction of (mean - L) H_k cancelled to
+    1.1e-9 .. 2.3e-9 of the row (5.8e-10 .. 7.3e-10 at 600-window segments) next to DC; the median level keeps
+    every window at <= 7e-12.  The data is well conditioned: the oracle is 1.5e-12 from numpy.fft here."""
+    n, nwin = 512, 700
+    c = 600 if seg == 600 else 3 * seg
+    s = synth.random_walk(nwin + n - 1, seed=n + c)
+    s[c] += 100.0
+    got = slide_model(s, n, window, "mean", seg)
+    want = oracle.batch_spectrum(s, n, 1, "mean", window)
+    kmin, kmax = oracle.band(n)
+    assert oracle.rel_err(got, want) <= 1e-10
+    assert oracle.inband_err(got, want, kmin, kmax) <= 1e-10
+
+
+@pytest.mark.parametrize("detrend", ["none", "mean"])
+@pytest.mark.parametrize("kind", [np.nan, np.inf, np.finfo(float).max])
+@pytest.mark.parametrize("c", [300, 293, 1210])
+def test_slide_model_missing_sample_isolated(c, kind, detrend):
+    """A NaN / Inf / DBL_MAX (MQL5's EMPTY_VALUE) sample on a 100-window segment's first sample, leaving
+    mid-segment, or entering the last window only: the windows that do not hold it keep the bar against the
+    oracle (fed to the trackers unchanged it left 99 resp. 6 clean windows of its segment NaN), the ones that do
+    are NaN rows."""
+    n, nwin, seg = 512, 700, 100
+    s = synth.random_walk(nwin + n - 1, seed=n + c)
+    s[c] = kind
+    clean, dirty = _split(nwin, n, c)
+    assert clean.sum() >= nwin // 2
+    got = slide_model(s, n, "hann", detrend, seg)
+    want = oracle.batch_spectrum(s, n, 1, detrend, "hann")
+    kmin, kmax = oracle.band(n)
+    assert np.isfinite(want[clean]).all() and np.isfinite(got[clean]).all()
+    assert oracle.rel_err(got[clean], want[clean]) <= 1e-10
+    assert oracle.inband_err(got[clean], want[clean], kmin, kmax) <= 1e-10
+    assert np.isnan(got[dirty]).all()
 
 
 def _hi(p):
