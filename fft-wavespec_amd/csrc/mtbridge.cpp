@@ -344,9 +344,12 @@ int get_slide_table(int dev, int log2n, int window, void **out) {
 constexpr int64_t kSlideMaxSegment = 2048;
 
 // ----------------------------------------------------------------- config
-enum Op : int { kOpSpectrum = 0, kOpInverse = 1 };
+enum Op : int { kOpSpectrum = 0, kOpInverse = 1, kOpFilter = 2 };
 struct Config {
     int op = kOpSpectrum;  // kOpInverse: rows of packed spectra -> rows of samples
+                           // kOpFilter: forward FFT, real mask, inverse / last sample in one launch (fp64)
+    int filter_mode = MTB_FILTER_SERIES;  // kOpFilter: MTB_FILTER_SERIES (N samples) or MTB_FILTER_LAST ([x_f[N-1], peak])
+    const double *d_mask = nullptr;       // kOpFilter: the launch's mask on its device (N doubles; plan- or batch-owned)
     int n = 0, log2n = 0;
     int64_t hop = 0, n_windows = 0;
     int detrend = 0, window = 0, trend_period = 0, output = 0;
@@ -364,6 +367,7 @@ struct Config {
     bool f32 = false;
     size_t elem() const { return f32 ? sizeof(float) : sizeof(double); }
     int64_t record() const {
+        if (op == kOpFilter) return filter_mode == MTB_FILTER_LAST ? 2 : n;
         if (op == kOpInverse || output == MTB_OUT_PACKED) return n;
         switch (output) {
         case MTB_OUT_TOPK: return 4 * topk;
@@ -438,7 +442,7 @@ WsLayout ws_layout(const Config &c, int dev) {
     const size_t es = c.elem();
     const bool large = c.op == kOpSpectrum && c.log2n > kMaxLog2N;
     size_t det = 0, means = 0, y = 0;
-    if (c.op == kOpSpectrum && (c.detrend == MTB_DETREND_KALMAN || (large && c.detrend == MTB_DETREND_IIR)))
+    if ((c.op == kOpSpectrum || c.op == kOpFilter) && (c.detrend == MTB_DETREND_KALMAN || (large && c.detrend == MTB_DETREND_IIR)))
         det = (size_t)(c.n_windows * c.n) * es;
     if (large && c.detrend == MTB_DETREND_MEAN) means = (size_t)c.n_windows * sizeof(double);
     if (large) y = (size_t)std::min<int64_t>(c.n_windows, c.chunk_windows()) * (size_t)(c.n / 2) * 2 * es;
@@ -706,6 +710,11 @@ int enqueue(int dev, const Config &c, const double *kalman, const void *d_series
     L.kmin = c.kmin;
     L.kmax = c.kmax;
     L.variant = (c.output == MTB_OUT_TOPK_PHASE || c.output == MTB_OUT_PHASE) ? c.variant : 0;
+    if (c.op == kOpFilter) {
+        L.output = c.filter_mode == MTB_FILTER_LAST ? kOutFiltLast : kOutFiltSeries;
+        L.mask = c.d_mask;
+        L.variant = 0;
+    }
     if (L.detrend == kDetrendIir) {
         // L/WaveSpecZZ_1.0.2.mq5:3041-3043, same double expressions as the CPU path
         const double omega = 2.0 * M_PI / c.trend_period;
@@ -718,7 +727,7 @@ int enqueue(int dev, const Config &c, const double *kalman, const void *d_series
             p = p * p;
         }
     }
-    HIP_OR(launch_spectrum(L, s), MTB_INTERNAL_ERROR);
+    HIP_OR(launch_spectrum(L, s), MTB_INTERNAL_ERROR);  // kOpFilter: launch_spectrum's output switch
     return MTB_OK;
 }
 
@@ -814,7 +823,8 @@ struct Part {
     bool recorded = false;  // `done` follows every command of the part
     int64_t w0 = 0, nw = 0;
     void *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr;
-    size_t in_bytes = 0, out_bytes = 0, ws_bytes = 0;
+    void *d_mask = nullptr;  // kOpFilter: this part's device copy of the batch's mask
+    size_t in_bytes = 0, out_bytes = 0, ws_bytes = 0, mask_bytes = 0;
 };
 struct Batch {
     Config cfg;
@@ -822,6 +832,8 @@ struct Batch {
     std::vector<Part> parts;
     void *h_in = nullptr, *h_out = nullptr;  // pinned staging (h_out: async jobs; synchronous calls use the ring)
     size_t h_in_bytes = 0, h_out_bytes = 0;
+    void *h_mask = nullptr;                  // kOpFilter: pinned copy of the caller's mask (all ones for a null mask)
+    size_t h_mask_bytes = 0;
     std::vector<void *> ring;                // synchronous calls: pinned output slots, part i -> ring[i % size]
     std::map<int64_t, int64_t> staged;       // series element ranges [first, second) already in h_in
     size_t ring_bytes = 0;
@@ -836,8 +848,10 @@ struct Batch {
             dev_free(p.dev, p.d_in, p.in_bytes);
             dev_free(p.dev, p.d_out, p.out_bytes);
             dev_free(p.dev, p.d_ws, p.ws_bytes);
+            dev_free(p.dev, p.d_mask, p.mask_bytes);
         }
         host_free(h_in, h_in_bytes);
+        host_free(h_mask, h_mask_bytes);
         host_free(h_out, h_out_bytes);
         for (void *r : ring) host_free(r, ring_bytes);
     }
@@ -944,9 +958,15 @@ void stage_out(double *dst, const void *src, int64_t n, bool f32) {  // pinned r
 #ifndef WSP_PART_BYTES
 #define WSP_PART_BYTES (64 << 20)  // the sanitizer builds (tests/hostsan) cut at 64 KiB to exercise many parts
 #endif
-int batch_plan(Session &S, const Config &c, std::unique_ptr<Batch> *out, bool ring) {
+int batch_plan(Session &S, const Config &c, std::unique_ptr<Batch> *out, bool ring, const double *mask = nullptr) {
     auto b = std::make_unique<Batch>();
     b->cfg = c;
+    if (c.op == kOpFilter) {  // the caller's mask is not read after this copy
+        b->h_mask_bytes = (size_t)c.n * sizeof(double);
+        if (!(b->h_mask = host_alloc(b->h_mask_bytes))) return MTB_NO_MEM;
+        double *hm = static_cast<double *>(b->h_mask);
+        for (int i = 0; i < c.n; ++i) hm[i] = mask ? mask[i] : 1.0;
+    }
     {
         std::lock_guard<std::mutex> lk(g_kalman_mu);
         memcpy(b->kalman, g_kalman, sizeof(g_kalman));
@@ -1001,6 +1021,12 @@ int part_enqueue(Batch &b, int i, const double *series, bool ring) {
     P.d_out = dev_alloc(P.dev, P.out_bytes);
     if (P.ws_bytes) P.d_ws = dev_alloc(P.dev, P.ws_bytes);
     if (!P.d_in || !P.d_out || (P.ws_bytes && !P.d_ws)) return MTB_NO_MEM;
+    if (c.op == kOpFilter) {
+        P.mask_bytes = b.h_mask_bytes;
+        if (!(P.d_mask = dev_alloc(P.dev, P.mask_bytes))) return MTB_NO_MEM;
+        HIP_OR(hipMemcpyAsync(P.d_mask, b.h_mask, P.mask_bytes, hipMemcpyHostToDevice, P.stream), MTB_INTERNAL_ERROR);
+        pc.d_mask = static_cast<const double *>(P.d_mask);
+    }
     P.done = event_alloc(P.dev);
     if (!P.done) return MTB_INTERNAL_ERROR;
     const int64_t e0 = P.w0 * c.hop, e1 = e0 + pc.series_elems();
@@ -1083,14 +1109,15 @@ int batch_copy_out(const Batch &b, double *out, int64_t out_cap, int32_t *n_out)
 // with nothing left to enqueue it waits for the oldest slot.  Slot j is refilled (outs[j + R]) once drained.
 // Only the parts holding records below out_cap are copied.
 constexpr int kRingSlots = 4;
-int run_sync(const Config &c, const double *series, double *out, int64_t out_cap, int32_t *out_len) {
+int run_sync(const Config &c, const double *series, double *out, int64_t out_cap, int32_t *out_len,
+             const double *mask = nullptr) {
     auto S = session();
     if (!S) {
         set_error("gpu_init has not succeeded (no GPU session)");
         return MTB_BACKEND_UNAVAILABLE;
     }
     std::unique_ptr<Batch> bp;
-    int st = batch_plan(*S, c, &bp, true);
+    int st = batch_plan(*S, c, &bp, true, mask);
     if (st != MTB_OK) return st;
     Batch &b = *bp;
     const int64_t rec = c.record();
@@ -1204,8 +1231,9 @@ struct Plan {
     double kalman[16];
     std::shared_ptr<void> ws;
     size_t ws_bytes = 0;
-    hipEvent_t done = nullptr;       // the last workspace execute's completion
+    hipEvent_t done = nullptr;       // the last workspace (or filter) execute's completion
     bool done_recorded = false;
+    std::shared_ptr<void> mask;      // filter plans: N doubles on the device (wsp_plan_set_mask), all ones at creation
     ~Plan() {
         if (done) (void)hipEventDestroy(done);
     }
@@ -2025,6 +2053,103 @@ MTB_API int64_t wsp_plan_create_inverse(int32_t device, int32_t window_len, int6
     return plan_register(std::move(p));
 }
 
+// The fused spectral band-pass (L/WaveSpecZZ_1.0.4-core.mq5:561-578): spectrum_config's checks, then the
+// filter's own -- all before the session lookup.
+static int filter_config(int32_t window_len, int64_t hop, int64_t n_windows, int32_t detrend, int32_t window,
+                         int32_t trend_period, int32_t mode, Config *c) {
+    if (mode != MTB_FILTER_SERIES && mode != MTB_FILTER_LAST) {
+        set_error("mode=%d: MTB_FILTER_SERIES (0) or MTB_FILTER_LAST (1)", mode);
+        return MTB_BAD_ARGS;
+    }
+    const int st = make_config(window_len, hop, n_windows, detrend, window, trend_period, MTB_PREC_F64, MTB_OUT_PACKED, c);
+    if (st != MTB_OK) return st;
+    if (c->log2n > kMaxLog2N) {
+        set_error("window_len=%d: the spectral filter covers windows up to %d", window_len, 1 << kMaxLog2N);
+        return MTB_BAD_ARGS;
+    }
+    c->op = kOpFilter;
+    c->filter_mode = mode;
+    return MTB_OK;
+}
+
+MTB_API int32_t gpu_spectral_filter_batch(const double *series, int32_t series_len, int32_t window_len, int32_t hop,
+                                          int32_t detrend, int32_t window, int32_t trend_period, const double *mask,
+                                          int32_t mask_len, int32_t mode, double *out, int32_t out_cap,
+                                          int32_t *out_len) {
+    if (out_len) *out_len = 0;
+    if (!series) {
+        set_error("null series");
+        return MTB_BAD_ARGS;
+    }
+    if (window_len <= 0 || series_len < window_len || hop <= 0) {
+        set_error("series_len=%d window_len=%d hop=%d: need series_len >= window_len > 0, hop > 0", series_len,
+                  window_len, hop);
+        return MTB_BAD_ARGS;
+    }
+    if (mask ? mask_len != window_len : mask_len != 0) {
+        set_error("mask_len=%d: one value per packed element (window_len=%d), or 0 with a null mask", mask_len, window_len);
+        return MTB_BAD_ARGS;
+    }
+    Config c;
+    const int64_t nwin = 1 + ((int64_t)series_len - window_len) / hop;
+    const int st = filter_config(window_len, hop, nwin, detrend, window, trend_period, mode, &c);
+    if (st != MTB_OK) return st;
+    if (!out || out_cap < c.record()) {
+        set_error("out_cap=%d smaller than one record (%lld doubles)", out_cap, (long long)c.record());
+        return MTB_BAD_ARGS;
+    }
+    c.n_windows = std::min<int64_t>(c.n_windows, out_cap / c.record());  // only the records that fit are computed
+    return run_sync(c, series, out, out_cap, out_len, mask);
+}
+
+MTB_API int64_t wsp_plan_create_filter(int32_t device, int32_t window_len, int64_t hop, int64_t n_windows,
+                                       int32_t detrend, int32_t window, int32_t trend_period, int32_t mode) {
+    if (!plan_device_ok(device)) return 0;
+    auto p = std::make_shared<Plan>();
+    if (filter_config(window_len, hop, n_windows, detrend, window, trend_period, mode, &p->cfg) != MTB_OK) return 0;
+    p->dev = device;
+    {
+        std::lock_guard<std::mutex> lk(g_kalman_mu);
+        memcpy(p->kalman, g_kalman, sizeof(g_kalman));
+    }
+    Tables t;
+    if (get_tables(device, p->cfg.log2n, false, &t) != MTB_OK) return 0;
+    if (plan_ws_fit(*p) != MTB_OK) return 0;
+    const size_t bytes = (size_t)p->cfg.n * sizeof(double);
+    p->mask = plan_ws_alloc(device, bytes);
+    const std::vector<double> ones((size_t)p->cfg.n, 1.0);
+    if (!p->mask || hipMemcpy(p->mask.get(), ones.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("wsp_plan_create_filter: cannot allocate the plan's mask (%zu bytes)", bytes);
+        return 0;
+    }
+    return plan_register(std::move(p));
+}
+
+MTB_API int32_t wsp_plan_set_mask(int64_t plan, const double *host_mask, int32_t mask_len) {
+    std::shared_ptr<Plan> p = find_plan(plan);
+    if (!p) {
+        set_error("unknown plan %lld", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op != kOpFilter) {
+        set_error("plan %lld is not a filter plan", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
+    if (host_mask ? mask_len != p->cfg.n : mask_len != 0) {
+        set_error("mask_len=%d: one value per packed element (window_len=%d), or 0 with a null mask", mask_len, p->cfg.n);
+        return MTB_BAD_ARGS;
+    }
+    HIP_OR(hipSetDevice(p->dev), MTB_BACKEND_UNAVAILABLE);
+    // executes already enqueued keep the mask they were given: wait for the last one before overwriting it
+    if (p->done_recorded) HIP_OR(hipEventSynchronize(p->done), MTB_INTERNAL_ERROR);
+    const std::vector<double> ones(host_mask ? 0 : (size_t)p->cfg.n, 1.0);
+    HIP_OR(hipMemcpy(p->mask.get(), host_mask ? host_mask : ones.data(), (size_t)p->cfg.n * sizeof(double),
+                     hipMemcpyHostToDevice),
+           MTB_INTERNAL_ERROR);
+    return MTB_OK;
+}
+
 MTB_API int32_t wsp_plan_execute(int64_t plan, const void *d_series, void *d_out, void *hip_stream) {
     std::shared_ptr<Plan> p = find_plan(plan);  // keeps the plan (and its workspace) alive through the enqueue
     if (!p) {
@@ -2042,7 +2167,10 @@ MTB_API int32_t wsp_plan_execute(int64_t plan, const void *d_series, void *d_out
         std::lock_guard<std::mutex> lk(p->mu);
         c = p->cfg;
         ws = p->ws;
-        if (ws) {  // stateful on the device: ordered after the previous execute (struct Plan)
+        std::shared_ptr<void> mask = p->mask;  // held through the enqueue, like the workspace
+        c.d_mask = static_cast<const double *>(mask.get());
+        // filter plans record `done` as well: wsp_plan_set_mask waits for it before it overwrites the mask
+        if (ws || c.op == kOpFilter) {  // stateful on the device: ordered after the previous execute (struct Plan)
             if (!p->done) {
                 if (hipSetDevice(p->dev) != hipSuccess || hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
                     p->done = nullptr;
@@ -2090,6 +2218,10 @@ MTB_API int32_t wsp_plan_set_algorithm(int64_t plan, int32_t algo) {
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     if (algo < MTB_ALGO_AUTO || algo > MTB_ALGO_SLIDE) {
         set_error("algorithm %d: MTB_ALGO_AUTO, MTB_ALGO_FFT or MTB_ALGO_SLIDE", algo);
         return MTB_BAD_ARGS;
@@ -2116,6 +2248,10 @@ MTB_API int32_t wsp_plan_set_variant(int64_t plan, int32_t variant) {
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     p->cfg.variant = variant;
     return MTB_OK;
 }
@@ -2127,6 +2263,10 @@ MTB_API int32_t wsp_plan_set_scan_flags(int64_t plan, void *d_flags) {
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     p->cfg.scan_flags = static_cast<unsigned char *>(d_flags);
     return MTB_OK;
 }
@@ -2140,6 +2280,10 @@ MTB_API int32_t wsp_plan_set_slide_segment(int64_t plan, int64_t windows) {
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     const Config old = p->cfg;
     p->cfg.slide_seg = windows;
     const int sw = plan_ws_fit(*p);
@@ -2154,6 +2298,10 @@ MTB_API int32_t wsp_plan_set_seed_chain(int64_t plan, int32_t segments) {
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     p->cfg.seed_chain = segments;
     return MTB_OK;
 }
@@ -2165,6 +2313,10 @@ MTB_API int32_t wsp_plan_set_trace(int64_t plan, void *d_trace, int64_t capacity
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     p->cfg.trace = capacity > 0 ? static_cast<long long *>(d_trace) : nullptr;
     p->cfg.trace_cap = capacity;
     return MTB_OK;
@@ -2178,6 +2330,10 @@ MTB_API int32_t wsp_plan_set_chunk(int64_t plan, int64_t windows) {
         return MTB_BAD_ARGS;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    if (p->cfg.op == kOpFilter) {
+        set_error("plan %lld is a filter plan: only wsp_plan_set_mask and wsp_plan_set_grid apply", (long long)plan);
+        return MTB_BAD_ARGS;
+    }
     const Config old = p->cfg;
     p->cfg.chunk = windows;
     const int sw = plan_ws_fit(*p);

@@ -9,7 +9,10 @@
 //   -> real FFT (replaces FourierTransformManual L/WaveSpecZZ_1.0.2.mq5:938-974
 //      and the DLL's gpu_fft_real_forward, Include/imports.mqh:7)
 //   -> |X_k|^2, k < N/2 (FftProcessor::Run 1.1.0:529-530) or the packed
-//      out[2k]=Re, out[2k+1]=Im layout (1.1.0:522-528).
+//      out[2k]=Re, out[2k+1]=Im layout (1.1.0:522-528);
+//   or, fused behind the R2C step (kOutFiltSeries / kOutFiltLast), the spectral band-pass of the core
+//   indicator: real mask over the packed elements (L/WaveSpecZZ_1.0.4-core.mq5:394-401), then the inverse
+//   transform on the same LDS slot (:426) or only [last filtered sample, peak |Y|] (:326-339, :575-576).
 //
 // Design (DESIGN.md "Kernel"):
 //  * A window of N real samples is FFT'd as an M = N/2 point complex FFT of
@@ -230,6 +233,7 @@ template <typename T> struct SpecArgs {
     int topk, kmin, kmax;            // kOutTopK(Phase): k slots over bins [kmin, kmax]
     double alpha, c;                 // IIR trend (L/WaveSpecZZ_1.0.2.mq5:3041-3043)
     double apow[8];                  // alpha^(32 * 2^j)
+    const double *__restrict__ mask; // kOutFiltSeries / kOutFiltLast: N reals, one per packed element
 };
 
 // LDS element index (padded) where pass PASS writes its element i = q*R + r.
@@ -941,6 +945,10 @@ __device__ __forceinline__ void topk_phase_wave(const cpx<double> *xrow, int M, 
     }
 }
 
+// max that keeps a NaN once one operand is NaN (fmax drops it): the filter's peak of a window with a
+// non-finite sample must be NaN, not the maximum of the rest.
+template <typename T> __device__ __forceinline__ T nan_max(T m, T v) { return (v > m || v != v) ? v : m; }
+
 // Loads the 16 sample pairs of this thread for group g (pass-0 layout,
 // element (q, r) = z[(t + TPW q) + (M/R0) r]).  Inactive slots read window 0.
 template <typename T, int LOG2N, int VAR = 0>
@@ -1031,6 +1039,9 @@ __global__ __launch_bounds__((Blk<LOG2N, VAR>::BLOCK),(VAR & kVarSplitLds) ? ((V
                           (OUT == kOutPhase && TPW >= 128 ? 2 * NWV * 8 : 0) +
                           (OUT == kOutTopKPhase ? WPB * (M < 64 ? M : 64) * 4 : 0);
     static_assert(!kPhase || sizeof(T) == 8, "phase outputs are fp64");
+    constexpr bool kFilt = OUT == kOutFiltSeries || OUT == kOutFiltLast;
+    static_assert(!kFilt || sizeof(T) == 8, "the spectral filter is fp64");
+    static_assert(OUT != kOutFiltSeries || !kSplit, "the filtered series stages conj Z as 16-B complex (AoS slot)");
     constexpr bool kCosWin = WCLASS == kWinCos || WCLASS == kWinCos2;
     __shared__ __attribute__((aligned(16))) char smem[kMain + kScan];
     double *scanbuf = reinterpret_cast<double *>(smem + kMain);
@@ -1062,7 +1073,7 @@ __global__ __launch_bounds__((Blk<LOG2N, VAR>::BLOCK),(VAR & kVarSplitLds) ? ((V
     for (; g < g_end; g += g_step) {
         // split top-k + phase: every address and twiddle that depends on t is recomputed per window instead of being
         // hoisted out of the window loop -- the 168-VGPR budget of 3 waves per SIMD has no room for them
-        if constexpr ((OUT == kOutTopKPhase || OUT == kOutPhase) && kSplit) asm volatile("" : "+v"(t));
+        if constexpr ((OUT == kOutTopKPhase || OUT == kOutPhase || OUT == kOutFiltLast) && kSplit) asm volatile("" : "+v"(t));
         const int64_t w = g * WPB + slot;
         const bool active = w < a.n_windows;
         double xa[16], xb[16];
@@ -1321,17 +1332,18 @@ __global__ __launch_bounds__((Blk<LOG2N, VAR>::BLOCK),(VAR & kVarSplitLds) ? ((V
         constexpr T kS1 = kCosWin ? T(1) : T(0.5), kS2 = kCosWin ? T(1) : T(0.25);
         T *prow = reinterpret_cast<T *>(lbase);  // power row staged in this window's LDS slot
         constexpr bool kDirect = OUT == kOutPower && (VAR & kVarDirectStore);
-        if constexpr (OUT != kOutPacked && !kDirect) __syncthreads();  // every final-pass LDS read is done
+        if constexpr (OUT != kOutPacked && OUT != kOutFiltLast && !kDirect) __syncthreads();  // every final-pass LDS read is done
         // bin indices and twiddle of the R2C slots; for the split top-k + phase form recomputed here (pinned after the
         // barrier), so that neither the twiddle load nor the 16 staging addresses and bound tests are issued at the
         // top of the window and held (spilled) across its FFT
         int tb0 = t;
-        if constexpr ((OUT == kOutTopKPhase || OUT == kOutPhase) && kSplit) asm volatile("" : "+v"(tb0));
+        if constexpr ((OUT == kOutTopKPhase || OUT == kOutPhase || OUT == kOutFiltLast) && kSplit) asm volatile("" : "+v"(tb0));
         constexpr bool kPhaseSplit = OUT == kOutPhase && kSplit != 0;
         double pim[kPhaseSplit ? 16 : 1];  // split phase record: Im X of the R2C slots, held until the slot is free
         const cpx<T> wt = a.tw[tb0];
         const cpx<T> wlo = tb0 == 0 ? cpx<T>{T(0.98078528040323044913), T(-0.19509032201612826785)} : wt;  // W_N^(B/2)
         const cpx<T> whi = tb0 == 0 ? cpx<T>{T(0), T(1)} : wt;  // W16^-4: slot s >= 4 of thread 0 -> W16^(s-4)
+        T fsum = T(0), fmx = T(0);  // kOutFiltLast: this thread's part of x_f[N-1] and of max |Y[i]|
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             const cpx<T> A = u0[s], Bv = u1[7 - s];
@@ -1383,6 +1395,39 @@ __global__ __launch_bounds__((Blk<LOG2N, VAR>::BLOCK),(VAR & kVarSplitLds) ? ((V
                 cpx<T> *xrow = reinterpret_cast<cpx<T> *>(lbase);
                 xrow[pad16(ka)] = {kS1 * xa.re, kS1 * xa.im};
                 xrow[pad16(kb)] = {kS1 * xb.re, kS1 * xb.im};
+            } else if constexpr (kFilt) {
+                // spectral band-pass (L/WaveSpecZZ_1.0.4-core.mq5:394-401, real mask, mode 0): Y[i] = mask[i] P[i] over
+                // the packed elements, (Re, Im) of one bin = one 16-B mask load (the table stays in L2)
+                const d2v ma = *reinterpret_cast<const d2v *>(a.mask + 2 * ka);
+                const d2v mb = *reinterpret_cast<const d2v *>(a.mask + 2 * kb);
+                const cpx<T> ya = {(kS1 * xa.re) * ma.x, (kS1 * xa.im) * ma.y};
+                const cpx<T> yb = {(kS1 * xb.re) * mb.x, (kS1 * xb.im) * mb.y};
+                const bool self = tb0 == 0 && s == 4;  // ka = 0 (real DC, X_M = 0), kb = M/2
+                if constexpr (OUT == kOutFiltSeries) {
+                    // C2R pre-step of inverse_kernel (transform_kernels.hip) on the registers: conj Z_k, conj Z_(M-k)
+                    // with the twiddle W_N^ka the R2C step just used, in natural order in this window's slot
+                    cpx<T> *zrow = reinterpret_cast<cpx<T> *>(lbase);
+                    const cpx<T> e = {T(0.5) * (ya.re + yb.re), T(0.5) * (ya.im - yb.im)};
+                    const cpx<T> d = {T(0.5) * (ya.re - yb.re), T(0.5) * (ya.im + yb.im)};
+                    const cpx<T> o = cmul(cconj(wk), d);
+                    cpx<T> za = {e.re - o.im, -(e.im + o.re)}, zb = {e.re + o.im, e.im - o.re};
+                    if (self) {
+                        za = {T(0.5) * ya.re, T(-0.5) * ya.re};  // Y[1] ignored
+                        zb = yb;                                  // conj(conj X_(M/2))
+                    }
+                    zrow[pad16(ka)] = za;
+                    zrow[pad16(kb)] = zb;
+                } else {
+                    // x_f[N-1] = (Y[0] + 2 sum_(0<k<M) (Re Y_k cos th_k + Im Y_k sin th_k)) / N with W_N^k = (cos, -sin)
+                    // and W_N^(M-k) = -conj W_N^k; |Y[0]| is not part of the peak (core.mq5:326-339 starts at 1)
+                    const T ta = self ? T(0.5) * ya.re : ya.re * wk.re - ya.im * wk.im;
+                    const T tb = self ? yb.im : -(yb.re * wk.re + yb.im * wk.im);
+                    fsum += ta + tb;
+                    fmx = nan_max(fmx, self ? T(0) : fabs(ya.re));
+                    fmx = nan_max(fmx, fabs(ya.im));
+                    fmx = nan_max(fmx, fabs(yb.re));
+                    fmx = nan_max(fmx, fabs(yb.im));
+                }
             } else if (active) {  // packed: (Re, Im) of one bin is already one 16-B (8-B) store
                 v2 oa, ob;
                 oa.x = kS1 * xa.re;
@@ -1392,6 +1437,71 @@ __global__ __launch_bounds__((Blk<LOG2N, VAR>::BLOCK),(VAR & kVarSplitLds) ? ((V
                 *reinterpret_cast<v2 *>(a.out + w * N + 2 * ka) = oa;
                 *reinterpret_cast<v2 *>(a.out + w * N + 2 * kb) = ob;
             }
+        }
+        if constexpr (OUT == kOutFiltSeries) {
+            // ---- inverse transform on the same slot: forward Stockham passes over conj Z, z_n = conj(Y_n) / M,
+            // x[2n] = Re z_n, x[2n+1] = Im z_n (inverse_kernel).  The next group's first exchange (or IIR staging)
+            // starts with a barrier, i.e. after the final-pass reads below.
+            cpx<T> *zrow = reinterpret_cast<cpx<T> *>(lbase);
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < BPT0; ++q)
+#pragma unroll
+                for (int r = 0; r < R0; ++r) {
+                    const int b = t + TPW * q;
+                    v[q * R0 + r] = zrow[pad16_at<M / R0>(pad16(b), b, r)];
+                }
+#pragma unroll
+            for (int q = 0; q < BPT0; ++q) dft<T, R0>(&v[q * R0]);
+            exchange<kSplit, T, LOG2N, 0>(lbase, v, t);
+            mid_passes<kSplit, (VAR & kVarTwTable) != 0, T, LOG2N, 1>(lbase, v, a.tw, t);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                u0[r] = v[r];
+                u1[r] = v[8 + r];
+            }
+            if constexpr (G::NPASS > 1) {
+                twiddle<(VAR & kVarTwTable) != 0, T, 8>(u0, a.tw, 2 * bq0);
+                twiddle<(VAR & kVarTwTable) != 0, T, 8>(u1, a.tw, 2 * bq1);
+            }
+            dft<T, 8>(u0);
+            dft<T, 8>(u1);
+            if (active) {
+                constexpr T kScale = T(1) / T(M);
+                T *xo = a.out + w * N;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    __builtin_nontemporal_store(v2{u0[r].re * kScale, -u0[r].im * kScale},
+                                                reinterpret_cast<v2 *>(xo + 2 * (bq0 + B * r)));
+                    __builtin_nontemporal_store(v2{u1[r].re * kScale, -u1[r].im * kScale},
+                                                reinterpret_cast<v2 *>(xo + 2 * (bq1 + B * r)));
+                }
+            }
+        }
+        if constexpr (OUT == kOutFiltLast) {
+            // ---- [x_f[N-1], max_(i>=1) |Y[i]|]: the window's TPW threads (an aligned segment of a wave, or NWV waves)
+            constexpr int SW = TPW < 64 ? TPW : 64;
+#pragma unroll
+            for (int off = SW / 2; off >= 1; off >>= 1) {
+                fsum += __shfl_xor(fsum, off, SW);
+                fmx = nan_max(fmx, __shfl_xor(fmx, off, SW));
+            }
+            if constexpr (TPW >= 128) {  // one window per workgroup: combine its waves
+                __syncthreads();  // scanbuf reuse (the mean / IIR detrend of this window is done with it)
+                if ((tid & 63) == 0) {
+                    scanbuf[tid >> 6] = fsum;
+                    scanbuf[8 + (tid >> 6)] = fmx;
+                }
+                __syncthreads();
+                fsum = T(0);
+                fmx = T(0);
+#pragma unroll
+                for (int i = 0; i < NWV; ++i) {
+                    fsum += scanbuf[i];
+                    fmx = nan_max(fmx, scanbuf[8 + i]);
+                }
+            }
+            if (active && t == 0) *reinterpret_cast<v2 *>(a.out + 2 * w) = v2{fsum * (T(2) / T(N)), fmx};
         }
         // unwrapped phase / group delay of bins [16t, 16t + 16) (kept in registers
         // through the top-k scan for kOutTopKPhase)

@@ -58,6 +58,7 @@ template <typename T> SpecArgs<T> make_args(const SpectrumLaunch &L, int wpb) {
     a.topk = L.topk;
     a.kmin = L.kmin;
     a.kmax = L.kmax;
+    a.mask = L.mask;
     a.alpha = L.iir_alpha;
     a.c = L.iir_c;
     for (int j = 0; j < 8; ++j) a.apow[j] = L.iir_apow[j];
@@ -94,6 +95,16 @@ template <typename T, int LOG2N, int DETREND, int OUT> constexpr int default_var
                : OUT == kOutTopK                                          ? kCommonVar
                                                                           : (kVarNoPrefetch | kVarNtStore);
     // (phase record: the AoS form; the split form, wsp_plan_set_variant 2, measured slower, round 5)
+    // (spectral filter: the series form stages conj Z as 16-B complex in the window's slot -- the AoS exchange.  The
+    // last-sample form stages nothing after the forward transform: at N = 2048 / 4096 without the IIR detrend it
+    // takes the power path's split exchange at 3 waves per SIMD, with the thread index re-pinned per window as in
+    // the split top-k + phase form (unpinned it spills 12-44 B/lane at 168 VGPRs); at the other lengths the split
+    // form still spills (N = 32, 128, 1024) or cannot raise occupancy, so they keep the AoS form.  N = 16384 with
+    // the IIR detrend: the Hann/Hamming recurrence spills 8 B/lane at the 256-VGPR bound of the 512-thread
+    // workgroup, the rotation form does not)
+    if constexpr (OUT == kOutFiltLast && DETREND != kDetrendIir && LOG2N >= 11 && LOG2N <= 12) return kDefaultVar;
+    if constexpr (OUT == kOutFiltSeries || OUT == kOutFiltLast)
+        return (LOG2N == 14 && DETREND == kDetrendIir) ? (kCommonVar & ~kVarWinRec) : kCommonVar;
     return (OUT == kOutPhase) ? (kVarNoPrefetch | kVarNtStore)
            : (DETREND == kDetrendIir || OUT != kOutPower || (sizeof(T) == 4 && DETREND == kDetrendMean) || LOG2N > 12)
                ? kCommonVar
@@ -118,7 +129,8 @@ template <typename T, int LOG2N, int VAR> constexpr bool phase_prefix_fits(int k
 // N >= 1024 without the IIR detrend (the phase outputs measured within noise of the run-time form and would
 // double the longest translation unit); elsewhere a.nt still selects the loads at run time.
 template <typename T, int LOG2N, int DETREND, int OUT, int VAR> constexpr bool ct_nt_variant() {
-    return !(VAR & kVarNtLoad) && (OUT == kOutPower || OUT == kOutTopK) && LOG2N >= 10 && DETREND != kDetrendIir;
+    return !(VAR & kVarNtLoad) && (OUT == kOutPower || OUT == kOutTopK || OUT == kOutFiltLast) && LOG2N >= 10 &&
+           DETREND != kDetrendIir;
 }
 
 template <typename T, int LOG2N, int DETREND, int OUT, int WCLASS, int VAR = default_var<T, LOG2N, DETREND, OUT>()>
@@ -182,12 +194,21 @@ hipError_t dispatch_win(const SpectrumLaunch &L, hipStream_t s) {
 }
 
 // OSET selects the output modes one translation unit instantiates:
-// kSetBase = power / packed / top-k, kSetPhase = the fp64 phase outputs.
-enum OutSet : int { kSetBase = 0, kSetPhase = 1 };
+// kSetBase = power / packed / top-k, kSetPhase = the fp64 phase outputs, kSetFilter = the fp64 spectral filter.
+enum OutSet : int { kSetBase = 0, kSetPhase = 1, kSetFilter = 2 };
 
 template <typename T, int LOG2N, int DETREND, int OSET>
 hipError_t dispatch_out(const SpectrumLaunch &L, hipStream_t s) {
-    if constexpr (OSET == kSetPhase) {
+    if constexpr (OSET == kSetFilter) {
+        if constexpr (std::is_same_v<T, double>) {
+            switch (L.output) {
+            case kOutFiltSeries: return dispatch_win<T, LOG2N, DETREND, kOutFiltSeries>(L, s);
+            case kOutFiltLast: return dispatch_win<T, LOG2N, DETREND, kOutFiltLast>(L, s);
+            default: return hipErrorInvalidValue;
+            }
+        }
+        return hipErrorInvalidValue;
+    } else if constexpr (OSET == kSetPhase) {
         switch (L.output) {
         case kOutPhase: return dispatch_win<T, LOG2N, DETREND, kOutPhase>(L, s);
         case kOutTopKPhase: return dispatch_win<T, LOG2N, DETREND, kOutTopKPhase>(L, s);

@@ -6,6 +6,7 @@ namespace wsp {
 
 hipError_t launch_spectrum(const SpectrumLaunch &L, hipStream_t stream) {
     if (L.f32) return launch_spectrum_f32(L, stream);
+    if (L.output == kOutFiltSeries || L.output == kOutFiltLast) return launch_spectrum_filter(L, stream);
     if (L.output == kOutPhase || L.output == kOutTopKPhase) return launch_spectrum_phase(L, stream);
     if (L.log2n >= core::kSplitLog2N) return launch_spectrum_f64_hi(L, stream);
     return core::dispatch_n_range<double, core::kSetBase, 5, core::kSplitLog2N - 1>(L, stream);

@@ -15,7 +15,10 @@ constexpr int kMaxLog2N = 14;  // N = 16384
 constexpr int kBlock = 128;    // minimum threads per workgroup (2 waves); M/16 when larger
 
 enum Detrend : int { kDetrendNone = 0, kDetrendMean = 1, kDetrendIir = 2, kDetrendKalman = 3 };
-enum Output : int { kOutPower = 0, kOutPacked = 1, kOutTopK = 2, kOutPhase = 3, kOutTopKPhase = 4 };
+enum Output : int { kOutPower = 0, kOutPacked = 1, kOutTopK = 2, kOutPhase = 3, kOutTopKPhase = 4,
+                    // spectral band-pass (launch_spectrum_filter; not part of the public MTB_OUT_* enum): forward FFT,
+                    // real mask over the packed elements, then the inverse (N samples) or [x_f[N-1], max |Y[i >= 1]|]
+                    kOutFiltSeries = 5, kOutFiltLast = 6 };
 
 // Everything a spectrum launch needs; pointer types are erased so one
 // struct serves the f64 and f32 instantiations.
@@ -39,6 +42,7 @@ struct SpectrumLaunch {
     int nt_mode;          // non-temporal sample loads: 0 = auto (hop >= N), 1 = off, 2 = on
     int vec_mode;         // pair loads: 0 = auto (aligned only), 1 = scalar, 2 = vector even if unaligned
     int variant;          // wsp_plan_set_variant: kOutTopKPhase 1 = the AoS form (ablation)
+    const double *mask;   // kOutFiltSeries / kOutFiltLast: N doubles on the device, one per packed element
 };
 
 hipError_t launch_spectrum(const SpectrumLaunch &L, hipStream_t stream);
@@ -48,6 +52,9 @@ hipError_t launch_spectrum_phase(const SpectrumLaunch &L, hipStream_t stream);  
 hipError_t launch_spectrum_f64_hi(const SpectrumLaunch &L, hipStream_t stream);
 hipError_t launch_spectrum_f32_hi(const SpectrumLaunch &L, hipStream_t stream);
 hipError_t launch_spectrum_phase_hi(const SpectrumLaunch &L, hipStream_t stream);
+// kOutFiltSeries / kOutFiltLast (fp64; spectrum_filter.hip, log2 N >= 12 in spectrum_filter_hi.hip)
+hipError_t launch_spectrum_filter(const SpectrumLaunch &L, hipStream_t stream);
+hipError_t launch_spectrum_filter_hi(const SpectrumLaunch &L, hipStream_t stream);
 
 // Inverse real FFT of packed spectra (gpu_fft_real_inverse,
 // L/WaveSpecZZ_1.0.4-core.mq5:65,426): n_windows rows of N doubles in the

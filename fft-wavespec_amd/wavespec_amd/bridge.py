@@ -26,6 +26,7 @@ WINDOW = {"none": 0, "hann": 1, "hamming": 2, "blackman": 3, "bartlett": 4}
 PRECISION = {"f64": 0, "f32": 1}
 OUTPUT = {"power": 0, "packed": 1, "topk": 2, "phase": 3, "topk_phase": 4}
 PHASE_METHOD = {"unwrapped": 0, "wrapped": 1, "group_delay": 2}
+FILTER_MODE = {"series": 0, "last": 1}  # MTB_FILTER_SERIES / MTB_FILTER_LAST
 
 _d = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
@@ -58,6 +59,8 @@ SIGNATURES = {
     "gpu_submit_spectrum_batch": (C.c_int32, [_d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, C.c_int32, C.c_int32, _i64p]),
     "gpu_try_get_spectrum_batch": (C.c_int32, [C.c_int64, _d, C.c_int32, _i32p, _i32p]),
+    "gpu_spectral_filter_batch": (C.c_int32, [_d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              _d, C.c_int32, C.c_int32, _d, C.c_int32, _i32p]),
     "gpu_set_kalman_params": (C.c_int32, [_d, C.c_int32]),
     "gpu_register_host": (C.c_int32, [_d, C.c_int64]),
     "gpu_unregister_host": (C.c_int32, [_d]),
@@ -78,6 +81,9 @@ SIGNATURES = {
     "wsp_plan_create": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32]),
     "wsp_plan_create_inverse": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "wsp_plan_create_filter": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32]),
+    "wsp_plan_set_mask": (C.c_int32, [C.c_int64, _d, C.c_int32]),
     "wsp_plan_execute": (C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "wsp_plan_algorithmic_bytes": (C.c_int64, [C.c_int64]),
     "wsp_plan_destroy": (C.c_int32, [C.c_int64]),
@@ -247,6 +253,25 @@ def spectrum_topk_phase_batch(series: np.ndarray, window_len: int, hop: int, det
     return out[: n_out.value]
 
 
+def spectral_filter_batch(series: np.ndarray, window_len: int, hop: int, detrend="none", window="none",
+                          trend_period: int = 0, mask: np.ndarray | None = None, mode="series") -> np.ndarray:
+    """gpu_spectral_filter_batch: forward FFT, real mask over the packed elements and the inverse in one launch
+    (the core indicator's per-bar pipeline, L/WaveSpecZZ_1.0.4-core.mq5:561-578) -> (nwin, window_len) filtered
+    windows (mode "series") or (nwin, 2) [last filtered sample, max |Y[i >= 1]|] (mode "last").  mask: window_len
+    reals, one per packed element; None = all ones."""
+    s = np.ascontiguousarray(series, dtype=np.float64)
+    nwin = 1 + (s.size - window_len) // hop
+    rec = 2 if mode == "last" else window_len
+    out = np.empty((max(nwin, 0), rec), dtype=np.float64)
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
+    n_out = C.c_int32(0)
+    _check("gpu_spectral_filter_batch",
+           lib().gpu_spectral_filter_batch(_dptr(s), s.size, window_len, hop, DETREND[detrend], WINDOW[window],
+                                           trend_period, None if m is None else _dptr(m), 0 if m is None else m.size,
+                                           FILTER_MODE[mode], _dptr(out), out.size, C.byref(n_out)))
+    return out[: n_out.value]
+
+
 def submit_spectrum_batch(series: np.ndarray, window_len: int, hop: int, detrend="none", window="hann",
                           trend_period: int = 0, precision="f64", output="power") -> int:
     s = np.ascontiguousarray(series, dtype=np.float64)
@@ -329,6 +354,31 @@ class Plan:
         self.record = window_len
         self.series_len = n_windows * window_len
         return self
+
+    @classmethod
+    def filter(cls, device: int, window_len: int, hop: int, n_windows: int, detrend="none", window="none",
+               trend_period: int = 0, mode="series") -> "Plan":
+        """wsp_plan_create_filter: the fused spectral filter on device buffers (fp64); the mask starts as all
+        ones (set_mask).  d_out must not alias d_series."""
+        self = cls.__new__(cls)
+        self.handle = lib().wsp_plan_create_filter(device, window_len, hop, n_windows, DETREND[detrend], WINDOW[window],
+                                                   trend_period, FILTER_MODE[mode])
+        if self.handle == 0:
+            raise BridgeError("wsp_plan_create_filter", INTERNAL_ERROR, last_error())
+        self.window_len, self.hop, self.n_windows = window_len, hop, n_windows
+        self.output = "filter_" + mode
+        self.record = 2 if mode == "last" else window_len
+        self.series_len = (n_windows - 1) * hop + window_len
+        return self
+
+    def set_mask(self, mask: np.ndarray | None) -> None:
+        """wsp_plan_set_mask: window_len reals, one per packed element (None = all ones), copied into the plan's own
+        device buffer after the executes already enqueued."""
+        if mask is None:
+            _check("wsp_plan_set_mask", lib().wsp_plan_set_mask(self.handle, None, 0))
+            return
+        m = np.ascontiguousarray(mask, dtype=np.float64)
+        _check("wsp_plan_set_mask", lib().wsp_plan_set_mask(self.handle, _dptr(m), m.size))
 
     def set_topk(self, top_k: int, min_period: float, max_period: float) -> None:
         _check("wsp_plan_set_topk", lib().wsp_plan_set_topk(self.handle, top_k, min_period, max_period))

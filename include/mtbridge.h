@@ -224,6 +224,33 @@ MTB_API int32_t gpu_spectrum_topk_phase_batch(const double *series, int32_t seri
                                               int32_t top_k, double min_period, double max_period, double *out,
                                               int32_t out_cap, int32_t *out_len);
 
+/* Fused spectral band-pass: the per-bar pipeline of the "core" indicator
+ * (L/WaveSpecZZ_1.0.4-core.mq5: copy the last N closes :565-569, remove DC
+ * :204-222, gpu_fft_real_forward :345, multiply the packed spectrum by a real
+ * mask :394-401 with mask_is_complex = 0 and mode = 0, peak :326-339,
+ * gpu_fft_real_inverse :426, plot :575-576) for every window of a series in
+ * ONE launch: the packed spectrum never leaves the chip.  Per window w:
+ *   u = window(detrend(series[w*hop .. w*hop + window_len)))  (as gpu_spectrum_batch)
+ *   P = gpu_fft_real_forward(u);  Y[i] = mask[i] * P[i], i < window_len
+ *   (one real value per packed ELEMENT, not per bin; one mask for all windows;
+ *   a null mask with mask_len = 0 means all ones)
+ * MTB_FILTER_SERIES: the record is gpu_fft_real_inverse(Y), window_len doubles
+ *   (Y[1] ignored, X_(N/2) = 0, DC real).
+ * MTB_FILTER_LAST: the record is 2 doubles, [x_f[N-1], max_(1<=i<N) |Y[i]|]
+ *   -- the WaveBuffer / PowerBuffer pair; the inverse transform is not run,
+ *   x_f[N-1] = (Y[0] + 2 sum_(0<k<N/2) (Y[2k] cos(2 pi k/N) + Y[2k+1] sin(2 pi k/N))) / N.
+ * fp64 only; window_len: power of two, 32..16384; any hop >= 1.  A window with
+ * a non-finite sample yields NaN records; other windows are unaffected.
+ * `mask` is copied before the call returns and never retained.  mask_len must
+ * equal window_len (or be 0 with a null mask).  Only min(nwin, out_cap/record)
+ * records are written.  Synchronous. */
+#define MTB_FILTER_SERIES 0
+#define MTB_FILTER_LAST 1
+MTB_API int32_t gpu_spectral_filter_batch(const double *series, int32_t series_len, int32_t window_len, int32_t hop,
+                                          int32_t detrend, int32_t window, int32_t trend_period,
+                                          const double *mask, int32_t mask_len, int32_t mode,
+                                          double *out, int32_t out_cap, int32_t *out_len);
+
 /* Kalman 4D parameters for MTB_DETREND_KALMAN, in the order of the inputs
  * at L/WaveSpecZZ_1.0.3-pla-kalman-fast.mq5:886-901: follow_strength,
  * q_pos, q_vel, q_acc, q_jerk, adapt_gain, meas_noise, init_var_pos,
@@ -282,6 +309,22 @@ MTB_API int64_t wsp_plan_create(int32_t device, int32_t window_len, int64_t hop,
  * wsp_plan_execute reads n_windows packed spectra of window_len doubles and
  * writes n_windows rows of window_len samples. */
 MTB_API int64_t wsp_plan_create_inverse(int32_t device, int32_t window_len, int64_t n_windows);
+
+/* Device-resident filter plan (gpu_spectral_filter_batch on HBM buffers, fp64):
+ * wsp_plan_execute reads the series and writes n_windows records of window_len
+ * (MTB_FILTER_SERIES) or 2 (MTB_FILTER_LAST) doubles.  d_out must not alias
+ * d_series: overlapping windows are read while earlier records are written.
+ * The plan starts with an all-ones mask.  Its executes are ordered like those
+ * of a plan with a workspace.  wsp_plan_set_grid applies; the other tuning
+ * setters return MTB_BAD_ARGS on a filter plan. */
+MTB_API int64_t wsp_plan_create_filter(int32_t device, int32_t window_len, int64_t hop, int64_t n_windows,
+                                       int32_t detrend, int32_t window, int32_t trend_period, int32_t mode);
+/* Copies host_mask (mask_len = window_len doubles; NULL with mask_len 0 = all
+ * ones) into the plan's own device buffer, after every execute already
+ * enqueued has finished (the call waits for them); later executes use the new
+ * mask.  The buffer is released by wsp_plan_destroy.  MTB_BAD_ARGS for an
+ * unknown or non-filter plan or a wrong mask_len. */
+MTB_API int32_t wsp_plan_set_mask(int64_t plan, const double *host_mask, int32_t mask_len);
 
 /* Enqueues the hot path on `hip_stream` (a hipStream_t; NULL = the null
  * stream) reading d_series (device pointer, double or float per the plan's
@@ -420,7 +463,8 @@ MTB_API int32_t wsp_plan_set_grid(int64_t plan, int32_t workgroups);
 MTB_API int32_t wsp_plan_get_algorithm(int64_t plan);
 
 /* Bytes the plan's algorithm must move per execute: unique input samples
- * + output, for roofline accounting. */
+ * + output, for roofline accounting.  A filter plan's mask
+ * (window_len doubles, L2-resident) is not counted. */
 MTB_API int64_t wsp_plan_algorithmic_bytes(int64_t plan);
 
 /* Grouped hop = 1 plan: a multi-symbol batch in the WaveCyclesBatchFetcher
